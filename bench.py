@@ -15,13 +15,22 @@ bytes) that rank 0 expands, chunk by chunk behind the integration (--gather; str
 `value` = the clip's pixels / wall time).  Started without a launcher, bench.py re-executes
 itself under torch.distributed.run.
 
-Prints ONE JSON line on rank 0.  Besides the contract's fields it carries
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints
+the headline (`value`, `ms_per_step`, ...).  With --full the line also carries what takes runs
+of its own:
+  output_check : the other output form timed, and the two forms' whole streams compared
   roofline     : algorithmic HBM bytes of one chunk of frames / the duration of the chunk's
                  kernels (frame kernel + scan + offsets + expansion), HIP event pairs on the
                  launch stream
+  secondary    : the other configurations of SURVEY 8(d)
   cpu_baseline : the CPU oracle (a literal port of the reference's rayon loop + serial raw
                  sink) timed on this box's host cores over a bounded sample, thread sweep
   end_to_end   : host-buffer legs (PCIe-inclusive), never `value`
+  (N > 1: the layout-only exchange and the sink-per-rank leg beside the timed gather)
+
+--dump-outputs DIR (N = 1) writes what the last timed step handed its caller as float64 .npy
+files: the per-frame event offsets, every frame's events summed field by field, and a fixed
+seeded sample of the events (dump_outputs below).
 """
 import argparse
 import json
@@ -85,11 +94,19 @@ def parse_args():
                     help="N=1: what the timed step leaves in HBM: the raw sink's 9 / 11-byte records written by the expansion "
                          "itself (adder_hip_integrate_wire_device: the bytes of the .adder file between header and EOF -- what "
                          "north_star's sink takes and VERDICT r3 asked the expansion to emit; the default) or 12-byte AdderEvents "
-                         "(adder_hip_integrate_device; N>1 always: the gathers move events or records).  The other form is "
-                         "timed in the same process as `output_check` either way")
+                         "(adder_hip_integrate_device; N>1 always: the gathers move events or records).  With --full the other form "
+                         "is timed in the same process as `output_check` either way")
     ap.add_argument("--skip-roofline", action="store_true",
                     help="no per-launch timing passes (used under rocprofv3 so that only default launches are seen)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: output_check, roofline, secondary, end_to_end, cpu_baseline (each still "
+                         "subject to its --no-* / --skip-* switch) and, N > 1, the other exchange forms")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (N = 1)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    return args
 
 
 def respawn_under_launcher(args):
@@ -382,11 +399,13 @@ def main():
         wire["chunk"] = int(tc.item())
 
     elapsed, (n_events, merged_total) = timed(gather_mode, args.steps, args.warmup)
+    if args.dump_outputs:  # (before anything else reuses the step's buffers)
+        dump_outputs(args.dump_outputs, torch, d_events, d_offsets, n_events, wire_out, Cn)
     kernel_ms = hv.last_batch_ms()  # HIP events around the last step's frame loop
     records = wire.get("records") if gather_mode in ("records", "records-torch") else hv.last_batch_records()
 
     output_check = None
-    if world == 1 and not args.skip_roofline:
+    if args.full and world == 1 and not args.skip_roofline:
         # the same step with the OTHER output form, in this process (same context, same buffers), and the whole stream's
         # bytes checked: the expansion's records == the events serialised by the separate pass (adder_hip_wire_events_device)
         rec_b = 9 if Cn == 1 else 11
@@ -430,7 +449,7 @@ def main():
         wire["bytes"] = int(te[1].item())
         if (rank == 0 or gather_mode == "host") and gather_mode != "layout":
             assert merged_total == total_events, (merged_total, total_events)
-        if gather_mode != "layout":  # the cheaper exchange, as an extra key
+        if args.full and gather_mode != "layout":  # the cheaper exchange, as an extra key
             layout_elapsed, _ = timed("layout", layout_steps, 1)
 
     # ---- N > 1: the other two forms of the exchange as first-class legs of their own (each timed like the headline) ----
@@ -442,7 +461,8 @@ def main():
                                      "value": round(Wd * Ht * T / (layout_elapsed / layout_steps) / 1e6, 1), "unit": "Mpixels/s",
                                      "bytes_sent_per_rank_per_step": 8 * (T + 1),
                                      "what": "every rank keeps its band's stream in its own HBM; only the per-frame counts are all-gathered"}
-    if world > 1 and hg is not None and gather_mode in ("records", "cabi") and not share and os.environ.get("ADDER_BENCH_SCALE_LEGS", "1") == "1":
+    if args.full and world > 1 and hg is not None and gather_mode in ("records", "cabi") and not share and \
+            os.environ.get("ADDER_BENCH_SCALE_LEGS", "1") == "1":
         try:
             leg_steps = max(2, args.steps // 2)
             image, header = open_host_image()
@@ -467,7 +487,7 @@ def main():
     post_chunks = 1
     chunk_frames = hv.chunk_frames()
     records1 = records
-    if not args.skip_roofline:
+    if args.full and not args.skip_roofline:
         hv.set_launch_timing(True)
         step("none")
         k1_us, k1_frames = hv.last_launch_avg_us(), hv.last_launch_frames() or 1.0
@@ -559,7 +579,7 @@ def main():
             (W, H, C, FRAMES, DTM, "scene", "collapse", "delta_t") and crf == [0, 0, 10]
         cands = [("r06_traffic_default.json" if wire_out else "r06_traffic_events_output.json")]
         tname = next((n for n in cands if os.path.exists(os.path.join(ROOT, "profiles", n))), None)
-        if default_workload and world == 1 and tname:
+        if args.full and default_workload and world == 1 and tname:
             tj = json.load(open(os.path.join(ROOT, "profiles", tname)))
             tk = tj["kernels"]
             fpl = float(tj.get("frames_per_launch", 160.0 / 3.0))  # (round 4's collection carries no such key)
@@ -615,7 +635,6 @@ def main():
             "value_times": ("one GPU, no exchange" if world == 1 else gather_mode),
             "backend": "none" if world == 1 else ("gloo (shared-device debug)" if share else "nccl (RCCL)"),
         },
-        "output_check": output_check,
         "events_per_s": round(total_events / (elapsed / args.steps), 1),
         "events_per_pixel_frame": round(e_all, 5),
         "records_per_unit_frame": round(r0, 5),
@@ -624,7 +643,10 @@ def main():
                         "note": "the captured graph of a batch length is instantiated up to 6 times on the first batches "
                                 "and the fastest instance kept (the runtime binds the graph's two branches to hardware "
                                 "queues at instantiation; measured 1.86 vs 2.08 ms per step between instances)"},
-        "roofline": {
+    }
+    if args.full:
+        out["output_check"] = output_check
+        out["roofline"] = {
             "bound": "hbm",
             "kernel": ("one chunk of frames: adder_lp_kernel (the lean-runs step in packed bytes: crf 0, DeltaT; adder_lr_kernel in "
                        "AbsoluteT, adder_lean_kernel otherwise) + adder_scan_kernel (its blocks chain the frame offsets; adder_offsets_kernel for the other frame kernels) + adder_lpx_kernel "
@@ -664,8 +686,8 @@ def main():
             "note": "algorithmic bytes (SURVEY 8(d) with the real 16-byte state: 1 + 32/T_launch + 12 e per unit-frame) "
                     "over ALL kernels of a chunk; the pipeline really moves the parked records twice on top of that "
                     "(frame_kernel_actual / expansion_actual are those kernels' own bytes over their own durations)",
-        },
-        "roofline_one_frame_per_launch": {
+        }
+        out["roofline_one_frame_per_launch"] = {
             "bound": "hbm",
             "kernel": "adder_lean1w_kernel" if lean else "adder_frame_kernel",
             "pipeline": {"what": "the whole one-frame-per-launch chunk: %d frame-kernel launches + scan + offsets + expansion, "
@@ -688,8 +710,7 @@ def main():
                     "to the next dependent launch); with a pair around EVERY launch the event packets themselves add "
                     "~2 us (launch_avg_us_event_pair_per_launch).  rocprofv3's kernel duration of the same command is "
                     "in profiles/ (kernel stats, adder_lean1w_kernel)",
-        },
-    }
+        }
     if gather_mode in ("records", "records-torch"):
         out["records_over_the_wire"] = {
             "transport": "libadder_rccl.so C-ABI, streamed (adder_gather_records_begin / _push / _end)"
@@ -724,17 +745,17 @@ def main():
             "unit": "Mpixels/s",
             "note": "same step with only the per-frame counts all-gathered (the payload stays sharded in HBM)"}
 
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         # the other configurations of SURVEY 8(d), each with its own context and clip (the headline's stay alive)
         out["secondary"] = secondary_legs(args, torch, A)
-    if world == 1 and not args.no_end_to_end:
+    if args.full and world == 1 and not args.no_end_to_end:
         out["end_to_end"] = end_to_end(hv, d_frames, T, units, Wd, Ht, Cn)
         d_chunk = torch.zeros((T + 63) // 64, 65, dtype=torch.int64, device=dev)
         out["end_to_end"]["raw_file_image_sink"] = end_to_end_host_image(torch, A, hv, d_frames, d_events, d_chunk, T, Wd, Ht,
                                                                          Cn, tmode, args.delta_t_max, total_events)
         out["end_to_end"]["default_quality_raw"] = end_to_end_default_quality(torch, A, Wd, Ht)
         out["end_to_end"]["compressed_sink_config5"] = end_to_end_config5(torch, A)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         hv.reset()
         hv.integrate_device(d_frames, d_events, d_offsets, stream=stream)
         hv.finish()
@@ -749,6 +770,44 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 20  # events in events_sample.npy: 48 MB of float64
+
+
+def event_fields(torch, rec, wire, Cn):
+    """int64 columns x, y, c, d, t of a [n, record bytes] uint8 block of the raw sink's records (bincode big-endian,
+    include/adder_hip.h: 9 bytes without c on a 1-channel plane, 11 with Some(c)) or of a [n, 3] int32 block of
+    AdderEvents -- the same values whichever form the step wrote (c = ADDER_C_NONE on a 1-channel plane)."""
+    if wire:
+        b = rec.to(torch.int64)
+        be = lambda i, k: sum(b[:, i + j] << (8 * (k - 1 - j)) for j in range(k))  # noqa: E731
+        o = 0 if Cn == 1 else 2
+        c = torch.full_like(b[:, 0], 0xFF) if Cn == 1 else b[:, 5]
+        return torch.stack([be(0, 2), be(2, 2), c, b[:, 4 + o], be(5 + o, 4)], 1)
+    w = rec.to(torch.int64) & 0xFFFFFFFF
+    return torch.stack([w[:, 0] & 0xFFFF, w[:, 0] >> 16, w[:, 1] & 0xFF, (w[:, 1] >> 8) & 0xFF, w[:, 2]], 1)
+
+
+def dump_outputs(path, torch, d_out, d_offsets, n, wire, Cn):
+    """--dump-outputs: what the last timed step handed its caller, as float64 (every value is an integer below 2^53):
+      frame_offsets.npy [T + 1]     the event index at which every frame starts (d_offsets)
+      frame_sums.npy    [T, 5]      every frame's events summed field by field (x, y, c, d, t): covers the whole stream
+      events_sample.npy [k, 6]      event index, x, y, c, d, t of up to DUMP_SAMPLE events at indices drawn with a fixed seed
+    Decoded fields, not bytes, so that the two output forms (--output) dump the same arrays."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rb = 9 if Cn == 1 else 11
+    rec = d_out.view(torch.uint8).reshape(-1)[:n * rb].view(n, rb) if wire else d_out[:n]
+    offs = d_offsets.cpu().numpy()
+    assert int(offs[-1]) == n, (int(offs[-1]), n)
+    sums = torch.stack([event_fields(torch, rec[int(lo):int(hi)], wire, Cn).sum(0) for lo, hi in zip(offs[:-1], offs[1:])])
+    idx = np.unique(np.random.default_rng(0).integers(0, n, size=min(n, DUMP_SAMPLE))) if n else np.zeros(0, np.int64)
+    d_idx = torch.from_numpy(idx).to(d_out.device)
+    sample = torch.cat([d_idx[:, None], event_fields(torch, rec[d_idx], wire, Cn)], 1)
+    np.save(os.path.join(path, "frame_offsets.npy"), offs.astype(np.float64))
+    np.save(os.path.join(path, "frame_sums.npy"), sums.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "events_sample.npy"), sample.cpu().numpy().astype(np.float64))
 
 
 def cpu_baseline(d_frames, d_events, d_offsets, T, Cn, Wd, Ht, multi, tmode, args):

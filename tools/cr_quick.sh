@@ -5,7 +5,7 @@ OUT=gpurun_out/cr; mkdir -p $OUT
 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fuzz.py tests/test_host_mirror.py -x -q -m gpu \
   -k "crf0 or cb_kernel or fuzz or full_size or capacity or eager_and_graph or batch_lengths or model_fixtures or frame_ring or quality_change or long_static or second_opinion" 2>&1 | tail -8 | tee $OUT/tests.txt
 legs() {
-  env $1 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-end-to-end --skip-roofline 2>$OUT/err.txt | tail -1 | python -c "
+  env $1 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-end-to-end --skip-roofline 2>$OUT/err.txt | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 for l in d['secondary']:

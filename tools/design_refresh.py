@@ -1,5 +1,5 @@
-"""Puts the secondary-legs table of a bench.py JSON line into DESIGN.md section 5 (in place of the one there):
-python tools/design_refresh.py gpurun_out/<run>/bench.json"""
+"""Puts the secondary-legs table of a `bench.py --full` JSON line into DESIGN.md section 5 (in place of the one there):
+python tools/design_refresh.py <bench.json>"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tab = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "design_tables.py"), sys.argv[1]], capture_output=True, text=True, check=True).stdout.split("\n")

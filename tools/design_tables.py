@@ -1,4 +1,4 @@
-"""Markdown tables for DESIGN.md section 5 from a bench.py JSON line: python tools/design_tables.py gpurun_out/<run>/bench.json"""
+"""Markdown tables for DESIGN.md section 5 from a `bench.py --full` JSON line: python tools/design_tables.py <bench.json>"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]

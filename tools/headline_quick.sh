@@ -7,6 +7,6 @@ timeout 1500 python -X faulthandler -m pytest tests/test_gpu_parity.py tests/tes
 tail -3 $OUT/tests_full.txt
 fi
 for i in 1 2; do
-  python bench.py --steps 32 --warmup 3 --no-cpu-baseline --no-end-to-end --no-secondary 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --steps 32 --warmup 3 --no-cpu-baseline --no-end-to-end --no-secondary 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('headline', d['ms_per_step'], d['value'], r['frac'], r['frame_kernel_launch_us'], r['scan_offsets_expand_us'], r['chunk_us'])"
 done | tee $OUT/headline.txt

@@ -8,7 +8,7 @@ VARIANTS=${VARIANTS:-"default build/variants/libadder_hip_base.so"}
 for rep in $(seq $REPS); do
 for lib in $VARIANTS; do
   l=$lib; [ "$lib" = default ] && l=""
-  ADDER_HIP_LIB=$l python bench.py --steps 24 --warmup 3 --no-cpu-baseline --no-end-to-end --no-secondary 2>/dev/null | tail -1 | python -c "
+  ADDER_HIP_LIB=$l python bench.py --full --steps 24 --warmup 3 --no-cpu-baseline --no-end-to-end --no-secondary 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$lib', d['ms_per_step'], r['frame_kernel_launch_us'], r['scan_offsets_expand_us'])" >> gpurun_out/lr_ab_raw.txt
 done; done
 python - <<'PY'

@@ -12,7 +12,7 @@ for envs in "$@"; do
   i=$((i+1))
   echo "=== [$i] $envs"
   env $envs rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/s$i" -o b -- \
-      python "$REPO/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --skip-roofline $BENCH_ARGS > "$OUT/log$i.txt" 2>&1
+      python "$REPO/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --skip-roofline $BENCH_ARGS > "$OUT/log$i.txt" 2>&1
   f=$(find "$OUT/s$i" -name '*kernel_stats.csv' | head -1)
   python3 - "$f" <<'PY'
 import csv,sys

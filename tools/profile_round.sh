@@ -15,7 +15,7 @@ export TMPDIR=/tmp
 cd /tmp
 
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- \
-    python "$REPO/bench.py" --steps 5 --warmup 2 --secondary-ms 30 > "$OUT/bench_under_rocprof.log" 2>&1
+    python "$REPO/bench.py" --full --steps 5 --warmup 2 --secondary-ms 30 > "$OUT/bench_under_rocprof.log" 2>&1
 find "$OUT/stats" -name '*kernel_stats.csv' -exec cp {} "$OUT/${ROUND}_bench_kernel_stats.csv" \;
 find "$OUT/stats" -name '*domain_stats.csv' -exec cp {} "$OUT/${ROUND}_bench_domain_stats.csv" \;
 
