@@ -6,7 +6,7 @@ drive it.  The C++ mirror of the reference's Source/Video/Encoder surface lives 
 ../host/.
 """
 from ._native import (  # noqa: F401
-    AdderHipError, AdderHipParams, AdderFramerParams, AdderCompressedParams, EVENT_DTYPE, SPARSE_STEP_DTYPE, LIB_PATH, load,
+    AdderHipError, AdderHipParams, AdderFramerParams, AdderCompressedParams, EVENT_DTYPE, SPARSE_STEP_DTYPE, LIB_PATH,
     TIME_DELTA_T, TIME_ABSOLUTE_T, TIME_MIXED, MULTI_NORMAL, MULTI_COLLAPSE,
     CONTENT_STATIC, CONTENT_NOISE, CONTENT_SCENE, D_EMPTY, D_ZERO_INTEGRATION, D_MAX, C_NONE,
     KERNEL_LEAN, KERNEL_GENERIC, KERNEL_CONTINUOUS, KERNEL_BOUNDED, KERNEL_CONSTANT_RUNS, KERNEL_RUN_RECORDS, KERNEL_LEAN_RUNS, KERNEL_LEAN_RUNS_PACKED,
@@ -17,3 +17,13 @@ from .video import CRF, crf_feature_radius, HipVideo, raw_header, raw_events, ra
 from .framer import HipFramer, contiguous_run_segments, FRAMED_U8, DVS, FRAME_U8, FRAME_U16, FRAME_U32  # noqa: F401
 from .compressed import CompressedEncoder, compressed_decode  # noqa: F401
 from .quality import calculate_quality_metrics, calculate_mse, calculate_psnr  # noqa: F401
+from . import dvs as _dvs
+from .dvs import HipDvs, adder_to_dvs_file, DVS_EVENT_DTYPE, DAT_DTYPE  # noqa: F401
+
+
+def load():
+    """Loads libadder_hip.so and binds every symbol include/adder_hip.h, adder_framer.h, adder_compressed.h and
+    adder_dvs.h declare; raises if one is missing."""
+    L = _native.load()
+    _dvs.load()
+    return L

@@ -1,0 +1,167 @@
+/* examples/adder_to_dvs.c -- the reference's adder-to-dvs tool from plain C: a raw `.adder` file -> DVS events,
+ * Prophesee `.dat` (binary, default) or "t x y p" text lines.  The file is streamed through the device in batches of
+ * wire records (adder_dvs_convert_wire_device); with --reorder the whole output stays on the device and is sorted
+ * once at the end (adder_dvs_sort_device).
+ *
+ *   make -C adder-codec-rs_amd && gcc -O2 -Iinclude -I$ROCM_PATH/include -D__HIP_PLATFORM_AMD__ \
+ *       examples/adder_to_dvs.c -Ladder-codec-rs_amd -ladder_hip -L$ROCM_PATH/lib -lamdhip64 \
+ *       -Wl,-rpath,$PWD/adder-codec-rs_amd -o adder_to_dvs
+ *   ./adder_to_dvs in.adder out.dat [--text] [--theta 0.01] [--reorder] [--date "2024-01-01 00:00:00"]
+ */
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+
+#include "adder_dvs.h"
+
+#define BATCH_RECORDS (1u << 22)
+
+static int usage(void) {
+    fprintf(stderr, "usage: adder_to_dvs IN.adder OUT [--text] [--theta T] [--reorder] [--date \"Y-m-d H:M:S\"]\n");
+    return 2;
+}
+
+int main(int argc, char **argv) {
+    const char *in_path = NULL, *out_path = NULL, *date = NULL;
+    int text = 0, reorder = 0;
+    double theta = 0.01;
+    for (int i = 1; i < argc; ++i) {
+        if (!strcmp(argv[i], "--text"))
+            text = 1;
+        else if (!strcmp(argv[i], "--reorder"))
+            reorder = 1;
+        else if (!strcmp(argv[i], "--theta") && i + 1 < argc)
+            theta = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--date") && i + 1 < argc)
+            date = argv[++i];
+        else if (!in_path)
+            in_path = argv[i];
+        else if (!out_path)
+            out_path = argv[i];
+        else
+            return usage();
+    }
+    if (!in_path || !out_path) return usage();
+    char now[32];
+    if (!date) {
+        const time_t t = time(NULL);
+        strftime(now, sizeof now, "%Y-%m-%d %H:%M:%S", localtime(&t));
+        date = now;
+    }
+    if (text) reorder = 0; /* the reference only queues binary output */
+    const int fmt = text ? ADDER_DVS_OUT_EVENTS : ADDER_DVS_OUT_DAT;
+    const size_t rb = text ? sizeof(AdderDvsEvent) : 8;
+
+    FILE *f = fopen(in_path, "rb");
+    if (!f) return perror(in_path), 1;
+    uint8_t hdr[64];
+    const size_t hl = fread(hdr, 1, sizeof hdr, f);
+    AdderDvsParams p;
+    uint32_t header_bytes = 0, eb = 0;
+    if (adder_dvs_parse_header(hdr, hl, &p, &header_bytes, &eb) != ADDER_OK) {
+        fprintf(stderr, "%s: not a raw .adder file\n", in_path);
+        return 1;
+    }
+    p.theta = theta;
+    fseek(f, (long)header_bytes, SEEK_SET);
+    AdderDvs *dvs = NULL;
+    int rc = adder_dvs_create(&p, &dvs);
+    if (rc != ADDER_OK) {
+        fprintf(stderr, "adder_dvs_create -> %d: %s\n", rc, adder_dvs_last_error(NULL));
+        return 1;
+    }
+    FILE *g = fopen(out_path, "wb");
+    if (!g) return perror(out_path), 1;
+    const size_t hn = adder_dvs_header_bytes(p.width, p.height, date, !text, NULL, 0);
+    char *hbuf = malloc(hn);
+    adder_dvs_header_bytes(p.width, p.height, date, !text, hbuf, hn);
+    fwrite(hbuf, 1, hn, g);
+    free(hbuf);
+
+    uint8_t *h_in = malloc((size_t)BATCH_RECORDS * eb), *d_in = NULL;
+    uint8_t *h_out = malloc((size_t)BATCH_RECORDS * rb), *d_out = NULL;
+    size_t kept_cap = BATCH_RECORDS, kept_n = 0; /* --reorder: every record of the run, on the device */
+    uint8_t *d_kept = NULL;
+    if (hipMalloc((void **)&d_in, (size_t)BATCH_RECORDS * eb) != hipSuccess ||
+        hipMalloc((void **)&d_out, (size_t)BATCH_RECORDS * rb) != hipSuccess ||
+        (reorder && hipMalloc((void **)&d_kept, kept_cap * rb) != hipSuccess)) {
+        fprintf(stderr, "device allocation failed\n");
+        return 1;
+    }
+    char *text_buf = NULL;
+    size_t text_cap = 0;
+    uint64_t n_in = 0, n_out = 0;
+    int status = 0;
+    for (;;) {
+        const size_t n = fread(h_in, eb, BATCH_RECORDS, f);
+        if (n == 0) break;
+        if (hipMemcpy(d_in, h_in, n * eb, hipMemcpyHostToDevice) != hipSuccess) return 1;
+        uint64_t got = 0, bad = ADDER_DVS_NO_BAD_EVENT, consumed = 0;
+        rc = adder_dvs_convert_wire_device(dvs, d_in, n, fmt, d_out, BATCH_RECORDS, &got, &bad, &consumed, NULL);
+        if (rc != ADDER_OK && rc != ADDER_DVS_E_BAD_EVENT) {
+            fprintf(stderr, "convert -> %d: %s\n", rc, adder_dvs_last_error(dvs));
+            return 1;
+        }
+        if (reorder) {
+            if (kept_n + got > kept_cap) {
+                uint8_t *bigger = NULL;
+                while (kept_n + got > kept_cap) kept_cap *= 2;
+                if (hipMalloc((void **)&bigger, kept_cap * rb) != hipSuccess) return 1;
+                if (kept_n) hipMemcpy(bigger, d_kept, kept_n * rb, hipMemcpyDeviceToDevice);
+                hipFree(d_kept);
+                d_kept = bigger;
+            }
+            if (got) hipMemcpy(d_kept + kept_n * rb, d_out, got * rb, hipMemcpyDeviceToDevice);
+            kept_n += got;
+        } else if (got) {
+            hipMemcpy(h_out, d_out, got * rb, hipMemcpyDeviceToHost);
+            if (text) {
+                const size_t tn = adder_dvs_format_text((const AdderDvsEvent *)h_out, got, NULL, 0);
+                if (tn > text_cap) {
+                    free(text_buf);
+                    text_cap = tn;
+                    text_buf = malloc(text_cap);
+                }
+                adder_dvs_format_text((const AdderDvsEvent *)h_out, got, text_buf, text_cap);
+                fwrite(text_buf, 1, tn, g);
+            } else {
+                fwrite(h_out, rb, got, g);
+            }
+        }
+        n_out += got;
+        if (rc == ADDER_DVS_E_BAD_EVENT) {
+            fprintf(stderr, "event %llu cannot be converted: %s\n", (unsigned long long)(n_in + bad),
+                    adder_dvs_last_error(dvs));
+            n_in += bad;
+            status = 1;
+            break;
+        }
+        n_in += consumed;
+        if (consumed < n || n < BATCH_RECORDS) break; /* EOF record, or the end of the file */
+    }
+    if (reorder && status == 0 && kept_n) { /* an error leaves the queue unwritten, as in the reference */
+        rc = adder_dvs_sort_device(dvs, d_kept, kept_n, fmt, NULL);
+        if (rc != ADDER_OK) {
+            fprintf(stderr, "sort -> %d: %s\n", rc, adder_dvs_last_error(dvs));
+            return 1;
+        }
+        uint8_t *all = malloc(kept_n * rb);
+        hipMemcpy(all, d_kept, kept_n * rb, hipMemcpyDeviceToHost);
+        fwrite(all, rb, kept_n, g);
+        free(all);
+    }
+    fclose(g);
+    fclose(f);
+    printf("%llu ADDER events -> %llu DVS events\n", (unsigned long long)n_in, (unsigned long long)n_out);
+    hipFree(d_in);
+    hipFree(d_out);
+    hipFree(d_kept);
+    free(h_in);
+    free(h_out);
+    free(text_buf);
+    adder_dvs_destroy(dvs);
+    return status;
+}
