@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/adder_hip.h"
+#include "adder_batch_plan.hpp"
 #include "adder_kernels.h"
 
 using namespace adder;
@@ -89,16 +90,12 @@ struct AdderHipCtx {
     // ordered-compaction scratch: a ring of two chunks of frames (a chunk is stepped while the one before
     // it is scanned and expanded)
     uint8_t *park_ring = nullptr;    // [slots][num_waves][park_bytes]
-    uint32_t park_group_shift = 0;   // ring layout of temporally blocked batches (park_offset)
     // graph instances no longer wanted (tuning losers, evicted batch lengths): destroyed with the context.  This HIP
     // runtime (ROCm 7.0) crashed in hip::Graph::UpdateStreams at a later hipGraphLaunch of ANOTHER instance once a
     // few dozen instances had been destroyed mid-life (rocgdb backtrace; tests: 22 batch lengths on one context).
     std::vector<hipGraphExec_t> retired_execs;
     uint32_t park_bytes = 0;         // scratch of one segment of one frame (fixed-slot kinds)
-    // what the scratch ring is laid out for: fixed slots per segment and frame (lean records, Continuous staging), or
-    // one record log per segment and chunk (per-event records of the generic / bounded Collapse kernels: log_capacity)
-    enum ScratchKind { kScratchNone, kScratchLean, kScratchLean8, kScratchCont, kScratchLog2, kScratchLog3 };
-    ScratchKind scratch_kind = kScratchNone;
+    ScratchKind scratch_kind = kScratchNone;  // what the scratch ring is laid out for (adder_batch_plan.hpp)
     uint32_t log_cap = 0;            // records per (segment, chunk) region (log kinds)
     uint32_t *wofs_ring = nullptr;   // [slots][num_waves] log kinds: where a segment's run of a frame starts
     uint32_t *wcur = nullptr;        // [ring_chunks][num_waves] log cursors between the launches of a chunk
@@ -121,9 +118,9 @@ struct AdderHipCtx {
     uint32_t *wtot_ring = nullptr;   // [slots][num_waves]
     uint32_t *wpref_ring = nullptr;  // [slots][num_waves]
     uint32_t *ftot_ring = nullptr;   // [slots]
-    uint32_t chunk = 1, slots = 2, ring_chunks = 3;
+    uint32_t chunk = 1, slots = 2;
+    static constexpr uint32_t ring_chunks = 3;  // a chunk being stepped, one being scanned / expanded, one of slack between the two streams
     uint32_t lean_blocks_per_cu = 0, expand_blocks_per_cu = 0;  // walking grids of the lean path when > 0 (0 = full grids)
-    uint32_t gen_blocks_per_cu = 0, gen_expand_blocks_per_cu = 0;  // generic variants: 0 = full grids
     uint32_t frames_per_launch = kMaxFramesPerLaunch;  // temporal blocking depth of the frame kernels
     uint32_t num_waves = 0;
     // device-resident batch description (kernels take {BatchArgs*, f}) + its pinned host mirror
@@ -151,6 +148,7 @@ struct AdderHipCtx {
         int chosen = -1;          // settled
         int last = -1;            // candidate of the batch in flight
         int recheck = 0;          // extra runs of candidate 0 after the others (it ran first, on a cold chip)
+        uint32_t want = 1;        // candidates to try (variant_graph_candidates)
     };
     std::map<uint64_t, GraphTune> graphs;  // key: see get_graph
     uint64_t tune_key = 0;
@@ -158,9 +156,6 @@ struct AdderHipCtx {
     uint32_t graph_candidates = 6;
     bool use_graph = true;
     bool eager_two_streams = false;
-    // ADDER_HIP_CU_SPLIT=n (0 < n < CUs): spatial partitioning instead of time sharing -- the frame kernel of chunk k+1
-    // on a stream masked to n CUs (the same share of every XCD), scan / offsets / expansion of chunk k on a stream masked
-    // to the others; a batch's first frame-kernel run and last expansion have no partner and take the unmasked stream.
     uint32_t *status = nullptr;   // device status word
     uint64_t *d_rec_total = nullptr;  // parked records of the last batch (diagnostics)
     // [0]: adder_log_pack_kernel's total (written, never read back); [1] (as u32): the status word of
@@ -243,7 +238,6 @@ struct AdderHipCtx {
         hipGraphExec_t out_graph = nullptr;  // the slot's hand-over (wire scatter + frame_out) as ONE launch
         uint64_t out_key[6] = {0, 0, 0, 0, 0, 0};  // what that graph baked in
     } fslot[4];
-    std::vector<hipStream_t> dummy_streams;  // ADDER_HIP_RING_SKIP_STREAMS (diagnostic)
     // The per-frame ring's stream arrangement is MEASURED, like the graph instances: where the HIP runtime puts a stream among
     // its hardware queues decides whether a dependency between two streams is cheap or costs tens of microseconds, and nothing
     // in the API tells (one process ran the default-quality ring at 60 us per frame, the next at 115; profiles/r05_ring_queues.txt).
@@ -352,8 +346,7 @@ static void free_ctx(AdderHipCtx *c) {
     }
     if (c->frame_e) (void)hipEventDestroy(c->frame_e);
     if (c->out_s) (void)hipStreamDestroy(c->out_s);
-    if (c->in_s && c->in_s != c->out_s) (void)hipStreamDestroy(c->in_s);
-    for (hipStream_t d : c->dummy_streams) (void)hipStreamDestroy(d);
+    if (c->in_s) (void)hipStreamDestroy(c->in_s);
     for (hipStream_t d : c->ring_streams) (void)hipStreamDestroy(d);
     if (c->in_e) (void)hipEventDestroy(c->in_e);
     for (void *p : {(void *)c->snap.slab, (void *)c->snap.dv_integ, (void *)c->snap.dv_dt, (void *)c->snap.dv_bdt,
@@ -520,7 +513,7 @@ static int init_state(AdderHipCtx *c) {
 // (launch_frame_loop makes the step of chunk k wait for the expansion of chunk k-2).
 
 
-static int alloc_scratch(AdderHipCtx *c, AdderHipCtx::ScratchKind kind);
+static int alloc_scratch(AdderHipCtx *c, ScratchKind kind);
 static bool env_flag(const char *name) {
     const char *e = getenv(name);
     return e && atoi(e) != 0;
@@ -629,8 +622,7 @@ extern "C" int adder_hip_create(const AdderHipParams *params, AdderHipCtx **out)
             // separate allocations of this size all start on the same 2 MiB boundary, a wave then reads the same
             // offset of four planes at once, and whether those four streams fall on the same HBM channels was left
             // to the allocator (measured: the same build ran at 1.82 or 1.97 ms per step from context to context).
-            size_t skew = 4352;
-            if (const char *e = getenv("ADDER_HIP_PLANE_SKEW")) skew = (size_t)atoi(e) & ~(size_t)255;
+            const size_t skew = 4352;
             const size_t plane = (c->n_pad * sizeof(uint32_t) + 255) & ~(size_t)255;
             c->slab_bytes = 5 * (plane + skew) + 256;
             HIPCHK(c, dalloc(&c->state_slab, c->slab_bytes));
@@ -653,8 +645,8 @@ extern "C" int adder_hip_create(const AdderHipParams *params, AdderHipCtx **out)
             HIPCHK(c, dalloc(&c->cn_bdt, cnt));
             HIPCHK(c, dalloc(&c->cn_meta, cnt));
         }
-        { int rc_ = alloc_scratch(c, c->continuous ? AdderHipCtx::kScratchCont
-                                      : p.time_mode == ADDER_TIME_ABSOLUTE_T ? AdderHipCtx::kScratchLean : AdderHipCtx::kScratchLean8);
+        { int rc_ = alloc_scratch(c, c->continuous ? kScratchCont
+                                      : p.time_mode == ADDER_TIME_ABSOLUTE_T ? kScratchLean : kScratchLean8);
           if (rc_ != ADDER_OK) return rc_; }
         { int rc_ = alloc_batch_desc(c, 1024); if (rc_ != ADDER_OK) return rc_; }
         HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_result), sizeof(BatchResult), hipHostMallocDefault));
@@ -666,9 +658,7 @@ extern "C" int adder_hip_create(const AdderHipParams *params, AdderHipCtx **out)
             // scan must not queue behind a grid that fills every CU, or the expansion starts a whole kernel late
             int lo_prio = 0, hi_prio = 0;
             HIPCHK(c, hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
-            const char *pe = getenv("ADDER_HIP_S2_PRIORITY");
-            const int prio = pe ? atoi(pe) : hi_prio;
-            HIPCHK(c, hipStreamCreateWithPriority(&c->cap_s2, hipStreamNonBlocking, prio));
+            HIPCHK(c, hipStreamCreateWithPriority(&c->cap_s2, hipStreamNonBlocking, hi_prio));
         }
         HIPCHK(c, hipEventCreateWithFlags(&c->cap_e1, hipEventDisableTiming));
         for (hipEvent_t &e : c->cap_e2) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -684,8 +674,6 @@ extern "C" int adder_hip_create(const AdderHipParams *params, AdderHipCtx **out)
             c->lean_blocks_per_cu = lb ? (uint32_t)atoi(lb) : 0u;
             c->expand_blocks_per_cu = eb ? (uint32_t)atoi(eb) : 0u;
         }
-        if (const char *e = getenv("ADDER_HIP_GEN_BLOCKS_PER_CU")) c->gen_blocks_per_cu = (uint32_t)atoi(e);
-        if (const char *e = getenv("ADDER_HIP_GEN_EXPAND_BLOCKS_PER_CU")) c->gen_expand_blocks_per_cu = (uint32_t)atoi(e);
         if (const char *gc = getenv("ADDER_HIP_GRAPH_CANDIDATES")) c->graph_candidates = (uint32_t)std::max(1, atoi(gc));
         if (const char *fl = getenv("ADDER_HIP_FRAMES_PER_LAUNCH"))
             c->frames_per_launch = (uint32_t)std::max(1, std::min<int>(atoi(fl), kMaxFramesPerLaunch));
@@ -707,9 +695,7 @@ extern "C" int adder_hip_create(const AdderHipParams *params, AdderHipCtx **out)
     return ADDER_OK;
 }
 
-static void ring_timeline_report();  // (diagnostics: ADDER_HIP_RING_TIMING=2, below)
-extern "C" void adder_hip_destroy(AdderHipCtx *ctx) {
-    ring_timeline_report(); free_ctx(ctx); }
+extern "C" void adder_hip_destroy(AdderHipCtx *ctx) { free_ctx(ctx); }
 
 extern "C" const char *adder_hip_last_error(const AdderHipCtx *ctx) {
     return ctx ? ctx->err.c_str() : g_create_error.c_str();
@@ -925,37 +911,24 @@ extern "C" int adder_hip_set_time_mode(AdderHipCtx *c, uint8_t time_mode) {
 
 extern "C" uint32_t adder_hip_num_chunks(const AdderHipCtx *c) { return c ? c->num_chunks : 0; }
 
-// The most events one frame can emit: the lean step at most 3 per unit (root event, Collapse filler, pop_top's
-// event); the generic step its whole arena (<= max_depth levels) plus pop_top's event.
-static bool lean_possible(const AdderHipCtx *c, float time_spanned) {
-    return !c->generic_sticky && !c->perpx && !feature_needs_perpx(c) && c->p.multi_mode == ADDER_MULTI_COLLAPSE &&
-           (float)c->p.delta_t_max <= time_spanned;
-}
-// The bounded Collapse step (adder_pixel.hpp cb_step): Collapse with delta_t_max > time_spanned, a uniform c_thresh, and
-// every sum its prefix coordinates form an exact integer below 2^24 -- integer time_spanned, at most delta_t_max /
-// time + 1 frames of 8-bit intensities before the pop.  Anything else takes the generic step.
-static bool rr_possible(const AdderHipCtx *c, float T, bool pop_at_once_ok = false);
-static bool cb_possible(const AdderHipCtx *c, float T) {
-    if (c->p.multi_mode != ADDER_MULTI_COLLAPSE) return false;
-    return rr_possible(c, T);
-}
-// (the bounded regime's conditions without the mode; pop_at_once_ok: delta_t_max <= time_spanned is fine too -- Mode Normal,
-// where a new root is then popped in the frame it starts: adder_pixel.hpp kRrFlushPop)
-static bool rr_possible(const AdderHipCtx *c, float T, bool pop_at_once_ok) {
-    if (c->continuous || c->perpx || feature_needs_perpx(c)) return false;
-    if (c->frac_time_seen) return false;
-    static const bool off = [] { const char *e = getenv("ADDER_HIP_NO_CB"); return e && atoi(e) != 0; }();
-    if (off) return false;
-    const double dtm = (double)std::max(c->p.delta_t_max, c->dtm_max_seen);
-    if (!((float)c->p.delta_t_max > T) && !pop_at_once_ok) return false;
-    if (!(T >= 1.0f) || T != (float)(uint32_t)T || T > 65536.0f) return false;
-    if (dtm + 2.0 * T >= 8388608.0) return false;
-    if ((dtm / T + 3.0) * 255.0 >= 8388608.0) return false;
-    return true;
+static uint32_t launch_depth(const AdderHipCtx *c) { return c->running_enabled ? 1u : c->frames_per_launch; }
+// what the batch plan (adder_batch_plan.hpp) reads of the context, for a batch of num_frames frames of time_spanned
+static BatchPlanIn plan_input(const AdderHipCtx *c, uint32_t num_frames, float time_spanned) {
+    BatchPlanIn in{};
+    in.multi_mode = c->p.multi_mode; in.time_mode = c->p.time_mode; in.channels = c->p.channels;
+    in.delta_t_max = c->p.delta_t_max; in.dtm_max_seen = c->dtm_max_seen; in.ref_time = c->p.ref_time;
+    in.c_thresh = c->c_thresh; in.c_thresh_max = c->p.c_thresh_max;
+    in.n_units = c->n_units; in.max_depth = c->max_depth; in.launch_depth = launch_depth(c);
+    in.continuous = c->continuous; in.generic_sticky = c->generic_sticky; in.perpx = c->perpx;
+    in.needs_perpx = feature_needs_perpx(c); in.feature_path = feature_path(c);
+    in.cr_valid = c->cr_valid; in.frac_time_seen = c->frac_time_seen; in.cr_time = c->cr_time;
+    in.frames_done = c->frames_done; in.run_bound = c->run_bound;
+    in.records_only = c->records_only; in.wire_batch = c->wire_batch;
+    in.num_frames = num_frames; in.time_spanned = time_spanned;
+    return in;
 }
 static size_t worst_case_events_per_frame(const AdderHipCtx *c, float time_spanned) {
-    if (c->continuous) return (size_t)c->n_units * (c->max_depth + 3u);
-    return (size_t)c->n_units * (lean_possible(c, time_spanned) ? 3u : c->max_depth + 1u);
+    return worst_case_events_per_frame(plan_input(c, 1u, time_spanned));
 }
 extern "C" size_t adder_hip_max_events_per_frame(const AdderHipCtx *c) {
     return c ? worst_case_events_per_frame(c, (float)c->p.ref_time) : 0;
@@ -984,28 +957,20 @@ static int status_to_code(AdderHipCtx *c, uint32_t st) {
 // The budget is a third of what the device has free, at most 96 GiB (a 1080p plane takes 3 - 5 GiB at 64-frame
 // chunks; a 4K RGB one -- 12 times the units -- needs 88 GiB for 64-frame chunks of per-event logs and fell to 48-frame
 // chunks under round 4's 64 GiB: a 64-frame batch then paid the state's round trip twice).
-static size_t scratch_bytes_per_chunk(const AdderHipCtx *c, AdderHipCtx::ScratchKind kind, uint32_t chunk) {
+static size_t scratch_bytes_per_chunk(const AdderHipCtx *c, ScratchKind kind, uint32_t chunk) {
     switch (kind) {
-        case AdderHipCtx::kScratchLean: return (size_t)c->num_waves * chunk * kLeanParkBytes;
-        case AdderHipCtx::kScratchLean8: return (size_t)c->num_waves * chunk * kLeanPark8Bytes;
-        case AdderHipCtx::kScratchCont:
+        case kScratchLean: return (size_t)c->num_waves * chunk * kLeanParkBytes;
+        case kScratchLean8: return (size_t)c->num_waves * chunk * kLeanPark8Bytes;
+        case kScratchCont:
             return (size_t)c->num_waves * chunk * (kWaveUnits + kWaveUnits * (c->max_depth + 3u) * kGenRecBytes);
-        case AdderHipCtx::kScratchLog2: return (size_t)c->num_waves * log_capacity(chunk, c->max_depth, true) * kGenRecBytes;
-        case AdderHipCtx::kScratchLog3: return (size_t)c->num_waves * log_capacity(chunk, c->max_depth, false) * kGenRecBytes;
+        case kScratchLog2: return (size_t)c->num_waves * log_capacity(chunk, c->max_depth, true) * kGenRecBytes;
+        case kScratchLog3: return (size_t)c->num_waves * log_capacity(chunk, c->max_depth, false) * kGenRecBytes;
         default: return 0;
     }
 }
-static uint32_t park_group_shift_wanted() {
-    if (const char *e = getenv("ADDER_HIP_PARK_GROUP_SHIFT")) {  // 0, or >= log2(segments per expansion wave)
-        const int sh = atoi(e);
-        static_assert(16 % ADDER_EXPAND_SEGS == 0, "a group (and a rotation group of 16 segments) must hold whole expansion waves");
-        return sh <= 0 ? 0u : (uint32_t)std::max(sh, 4);
-    }
-    return 4u;
-}
-static int alloc_scratch(AdderHipCtx *c, AdderHipCtx::ScratchKind kind) {
+static int alloc_scratch(AdderHipCtx *c, ScratchKind kind) {
     // (a Collapse context that has the general log can run the bounded step on it: no thrash between the two)
-    if (c->park_ring && (c->scratch_kind == kind || (c->scratch_kind == AdderHipCtx::kScratchLog3 && kind == AdderHipCtx::kScratchLog2)))
+    if (c->park_ring && (c->scratch_kind == kind || (c->scratch_kind == kScratchLog3 && kind == kScratchLog2)))
         return ADDER_OK;
     for (auto &kv : c->graphs)  // they bake the chunking
         for (hipGraphExec_t e : kv.second.cand)
@@ -1017,19 +982,12 @@ static int alloc_scratch(AdderHipCtx *c, AdderHipCtx::ScratchKind kind) {
     c->wtot_ring = c->wpref_ring = c->ftot_ring = c->wofs_ring = c->wcur = nullptr;
     c->park_bytes = 0;
     c->log_cap = 0;
-    c->scratch_kind = AdderHipCtx::kScratchNone;
+    c->scratch_kind = kScratchNone;
     for (void *p : old)
         if (p) HIPCHK(c, hipFree(p));
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
     const size_t budget = std::min<size_t>((size_t)96 << 30, free_b / 3);
-    c->ring_chunks = 3;  // a chunk being stepped, one being scanned / expanded, one of slack between the two streams
-    if (const char *e = getenv("ADDER_HIP_RING_CHUNKS")) c->ring_chunks = std::max(2, std::min(atoi(e), 4));
-    // default: groups of 16 segments -- the 16 segments an expansion wave reads of one frame are contiguous; contexts
-    // measured 1.515 - 1.525 ms per step (a few 1.57 - 1.58) against 1.55 / 1.62 (two modes) for the rotated
-    // segment-major layout (profiles/r03_ctx_spread.txt).  (A group must divide the segment count, which is padded to a
-    // multiple of 16: larger requests fall back to 16.)
-    c->park_group_shift = park_group_shift_wanted();
     uint32_t ch = kMaxChunk;
     while (ch > 1u && c->ring_chunks * (scratch_bytes_per_chunk(c, kind, ch) + (size_t)c->num_waves * ch * 12u) > budget) --ch;
     c->chunk = ch;
@@ -1040,19 +998,16 @@ static int alloc_scratch(AdderHipCtx *c, AdderHipCtx::ScratchKind kind) {
     HIPCHK(c, dalloc(&c->wpref_ring, (size_t)c->slots * c->num_waves));
     // events, then parked records per frame, then the scan's tile sums [slot][tile][2] (planes scanned in tiles)
     HIPCHK(c, dalloc(&c->ftot_ring, 2 * (size_t)c->slots + (size_t)c->slots * ((c->num_waves + kScanTileWaves - 1) / kScanTileWaves) * 2));
-    if (kind != AdderHipCtx::kScratchCont) {  // (the lean records of blocked batches go to logs too: lean_log_cap)
+    if (kind != kScratchCont) {  // (the lean records of blocked batches go to logs too: lean_log_cap)
         HIPCHK(c, dalloc(&c->wofs_ring, (size_t)c->slots * c->num_waves));
         HIPCHK(c, dalloc(&c->wcur, (size_t)c->ring_chunks * c->num_waves));
     }
-    if (kind == AdderHipCtx::kScratchLog2 || kind == AdderHipCtx::kScratchLog3) {
-        c->log_cap = log_capacity(c->chunk, c->max_depth, kind == AdderHipCtx::kScratchLog2);
+    if (kind == kScratchLog2 || kind == kScratchLog3) {
+        c->log_cap = log_capacity(c->chunk, c->max_depth, kind == kScratchLog2);
     } else {
         c->park_bytes = (uint32_t)(scratch_bytes_per_chunk(c, kind, 1u) / c->num_waves);
     }
     c->scratch_kind = kind;
-    if (getenv("ADDER_HIP_DEBUG_ADDRS"))
-        fprintf(stderr, "[adder_hip] slab %p park %p wtot %p wpref %p ftot %p chunk %u\n", (void *)c->state_slab, (void *)c->park_ring,
-                (void *)c->wtot_ring, (void *)c->wpref_ring, (void *)c->ftot_ring, c->chunk);
     return ADDER_OK;
 }
 
@@ -1076,7 +1031,6 @@ static int alloc_deep_planes(AdderHipCtx *c) {
 // K1, and the K1s of chunk k+2 wait for them (the scratch ring holds two chunks).  Running the
 // expansion inside K1's grid (round 1) no longer pays: with the lean step both kernels are bound by the
 // memory system, and a resident K1 grid leaves no wave slots for a concurrent kernel anyway.
-static uint32_t launch_depth(const AdderHipCtx *c) { return c->running_enabled ? 1u : c->frames_per_launch; }
 static Lean1wArgs lean1w_args(const AdderHipCtx *c) {
     return Lean1wArgs{c->hdr, c->integ0, c->dt0, c->bdt0, c->lastf, c->n_units, c->num_waves};
 }
@@ -1117,16 +1071,6 @@ static int launch_feature_loop(AdderHipCtx *c, uint32_t num_frames, uint32_t var
     return ADDER_OK;
 }
 
-// The integer-state kernels (lean runs, run records) keep their whole state in the header, delta_t and last_fired_t
-// planes; the other level-0 planes and the levels are derived from it (divisions, and for run records a store per level).
-// A launch that is followed by another launch of the same batch leaves them stale (variant bit 2048): only the batch's last
-// launch brings the planes to the resident form every other kernel, a rollback or the next batch reads.  (Run records:
-// 30 us of a 160 us launch were this epilogue.)
-static uint32_t lazy_state_bit(const AdderHipCtx *c, uint32_t variant, bool more_launches) {
-    static const bool off = env_flag("ADDER_HIP_NO_LAZY_STATE");
-    return (more_launches && (variant & (256u | 512u)) && !c->running_enabled && !off) ? 2048u : 0u;
-}
-
 static int launch_frame_loop(AdderHipCtx *c, uint32_t num_frames, uint32_t variant, hipStream_t s, hipStream_t s2,
                              bool timing) {
     // temporal blocking is off while the running-intensities side plane is wanted (per-frame
@@ -1139,9 +1083,9 @@ static int launch_frame_loop(AdderHipCtx *c, uint32_t num_frames, uint32_t varia
     // after the other (measured: the scan queued behind the resident frame kernel for a whole kernel time): both are
     // launched with a few workgroups per CU that walk their work, so that both are resident on every CU.
     const bool share = s2 != nullptr && num_frames > c->chunk;
-    const bool gen = (variant & 4u) != 0u;
-    const uint32_t lean_cap = share ? (gen ? c->gen_blocks_per_cu : c->lean_blocks_per_cu) * c->num_cus : 0u;
-    const uint32_t expand_cap = share ? (gen ? c->gen_expand_blocks_per_cu : c->expand_blocks_per_cu) * c->num_cus : 0u;
+    const bool walk = share && !(variant & kVarGeneric);  // (generic batches: full grids)
+    const uint32_t lean_cap = walk ? c->lean_blocks_per_cu * c->num_cus : 0u;
+    const uint32_t expand_cap = walk ? c->expand_blocks_per_cu * c->num_cus : 0u;
     uint32_t k = 0;
     for (uint32_t f0 = 0; f0 < num_frames; f0 += c->chunk, ++k) {
         const uint32_t nf = std::min(c->chunk, num_frames - f0);
@@ -1152,7 +1096,7 @@ static int launch_frame_loop(AdderHipCtx *c, uint32_t num_frames, uint32_t varia
         for (uint32_t f = f0; f < f0 + nf; f += depth) {
             const uint32_t nb = std::min(depth, f0 + nf - f);
             if (timing && !per_chunk) HIPCHK(c, hipEventRecord(c->launch_events[2 * c->timed_pairs], s));
-            HIPCHK(c, adder_launch_frame(c->d_batch, f, nb, variant | lazy_state_bit(c, variant, f + nb < num_frames), c->num_waves, lean_cap, s, &wide));
+            HIPCHK(c, adder_launch_frame(c->d_batch, f, nb, variant | variant_lazy_state_bit(variant, f + nb < num_frames, c->running_enabled), c->num_waves, lean_cap, s, &wide));
             if (timing) {  // the pair brackets the frame kernel (K1) only
                 if (!per_chunk) {
                     HIPCHK(c, hipEventRecord(c->launch_events[2 * c->timed_pairs + 1], s));
@@ -1180,13 +1124,9 @@ static int launch_frame_loop(AdderHipCtx *c, uint32_t num_frames, uint32_t varia
         // (a lean-runs batch that hands its records out: the scan also leaves the segments' record prefix, for the packing)
         // (the integer-state kernels' and the bounded Collapse kernel's batches: the scan's blocks chain the frame offsets
         // themselves, adder_scan_kernel CHAIN -- a launch less per chunk; those frame kernels zero the entries, chain_zero)
-        static const bool no_chain = env_flag("ADDER_HIP_NO_SCAN_CHAIN");
-        // (adder_launch_frame's order: Continuous, run records, constant runs, bounded Collapse, generic, packed / plain lean runs)
-        const bool chain_kernel = (variant & 8u) == 0u && ((variant & (512u | 128u | 32u)) != 0u ||
-                                                           ((variant & 4u) == 0u && (variant & (4096u | 256u)) != 0u));
-        const bool chain = chain_kernel && num_frames != 1u && !c->records_only && !no_chain;
+        const bool chain = variant_scan_chains(variant) && num_frames != 1u && !c->records_only;
         HIPCHK(c, adder_launch_scan(c->d_batch, f0, nf, c->num_waves, t, num_frames == 1u ? 1u : 0u,
-                                    (c->records_only && (variant & 256u)) ? 1u : 0u, chain ? 1u : 0u));
+                                    (c->records_only && (variant & kVarLeanRuns)) ? 1u : 0u, chain ? 1u : 0u));
         if (num_frames != 1u && !chain) HIPCHK(c, adder_launch_offsets(c->d_batch, f0, nf, t));  // (one frame: done by the scan)
         if (!c->records_only) HIPCHK(c, adder_launch_expand(c->d_batch, f0, nf, c->num_waves, variant, expand_cap, t, c->h_batch));
         if (timing) {
@@ -1206,8 +1146,7 @@ static int instantiate_graph(AdderHipCtx *c, uint32_t num_frames, uint32_t varia
     // per-event-record batches (generic / bounded Collapse kernels) are captured on ONE stream: their frame kernel is
     // bound by instruction issue at full occupancy and leaves the expansion no room to run beside it -- two branches
     // measured 10.5 us per 1080p frame against 10.0 in sequence (walking grids 11.6 - 14.2)
-    static const bool gen_two = [] { const char *e = getenv("ADDER_HIP_GEN_TWO_STREAMS"); return e && atoi(e) != 0; }();
-    hipStream_t s2 = (one_stream || ((variant & 4u) && !gen_two)) ? nullptr : c->cap_s2;
+    hipStream_t s2 = (one_stream || (variant & kVarGeneric)) ? nullptr : c->cap_s2;
     int rc = launch_frame_loop(c, num_frames, variant, c->cap_s, s2, false);
     hipError_t e = hipStreamEndCapture(c->cap_s, &graph);
     if (rc != ADDER_OK) {
@@ -1226,10 +1165,10 @@ constexpr int kTuneRecheckRuns = 2;
 
 static int get_graph(AdderHipCtx *c, uint32_t num_frames, uint32_t variant, hipGraphExec_t *out) {
     // everything the captured launch sequence depends on
-    // (running_enabled and the lazy-state switch decide the launches' lazy bits, lazy_state_bit)
+    // (running_enabled decides the launches' lazy bits, variant_lazy_state_bit)
     // (graph_slot: a frame slot of the per-frame ring has its own description, so its own graphs)
     // (bits: frames 0-23, variant 24-39, launch depth 40-47, running 48, frame slot 49-)
-    const uint64_t key = (uint64_t)(num_frames & 0xffffffu) | ((uint64_t)(variant & 0xffffu) << 24) | ((uint64_t)(launch_depth(c) & 0xffu) << 40) |
+    const uint64_t key = (uint64_t)(num_frames & 0xffffffu) | ((uint64_t)(variant & kVarKeyMask) << 24) | ((uint64_t)(launch_depth(c) & 0xffu) << 40) |
                          ((uint64_t)(c->running_enabled ? 1u : 0u) << 48) | ((uint64_t)c->graph_slot << 49);
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
@@ -1239,6 +1178,7 @@ static int get_graph(AdderHipCtx *c, uint32_t num_frames, uint32_t variant, hipG
             c->graphs.erase(c->graphs.begin());
         }
         it = c->graphs.emplace(key, AdderHipCtx::GraphTune{}).first;
+        it->second.want = variant_graph_candidates(variant, num_frames, c->chunk, c->graph_candidates);
     }
     AdderHipCtx::GraphTune &g = it->second;
     c->tune_pending = false;
@@ -1247,8 +1187,7 @@ static int get_graph(AdderHipCtx *c, uint32_t num_frames, uint32_t variant, hipG
         return ADDER_OK;
     }
     // still choosing: the newest candidate until it has had its runs, then one more candidate
-    // (a batch of a single chunk has no second branch to overlap: one candidate is all it needs)
-    const uint32_t want = (num_frames > c->chunk && !(variant & 4u)) ? std::max(1u, c->graph_candidates) : 1u;
+    const uint32_t want = g.want;
     int use = (int)g.cand.size() - 1;
     if (use > 0 && g.cand.size() >= want && g.runs[use] >= kTuneRunsPerCandidate && g.recheck < kTuneRecheckRuns) {
         // every candidate has had its runs: the first one (one stream) ran on a cold chip -- it gets two more now
@@ -1291,8 +1230,7 @@ static void graph_tune_report(AdderHipCtx *c, float ms) {
     if (g.last < 0 || g.chosen >= 0) return;
     g.runs[g.last] += 1;
     if (g.runs[g.last] > 1 || kTuneRunsPerCandidate == 1) g.ms[g.last] = std::min(g.ms[g.last], ms);
-    const uint32_t want = (c->pending_frames > c->chunk && !((c->tune_key >> 24) & 4u)) ? std::max(1u, c->graph_candidates) : 1u;  // (get_graph's: variant bit 2 = generic)
-    const bool all_ran = g.cand.size() >= want && g.runs.back() >= kTuneRunsPerCandidate;
+    const bool all_ran = g.cand.size() >= g.want && g.runs.back() >= kTuneRunsPerCandidate;
     if (all_ran && g.cand.size() > 1 && g.last == 0 && g.runs[0] > kTuneRunsPerCandidate) g.recheck += 1;
     if (all_ran && (g.cand.size() == 1 || g.recheck >= kTuneRecheckRuns)) {
         // (the one-stream instance keeps the batch unless a two-branch one beats it by more than the runs' own scatter)
@@ -1422,11 +1360,6 @@ static int ensure_lr_tab(AdderHipCtx *c, float time_spanned, hipStream_t stream)
 // Queues `num_frames` frames on `stream`.
 static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_frames, float time_spanned,
                           AdderEvent *d_out, size_t out_cap, uint64_t *d_offsets, hipStream_t stream) {
-    // Pixels deeper than one fired level cannot occur when Collapse pops the root as soon as
-    // it has accumulated once (delta_t_max <= time_spanned): then the lean kernel (adder_pixel.hpp
-    // lean_step) runs.  Once a generic batch has run, pixels may hold deeper arenas (or a root that
-    // the lean step's "time_spanned >= delta_t_max" folding does not describe), so the choice is sticky
-    // until adder_hip_reset: update_quality_manual can lower delta_t_max mid-stream (video.rs:1264-1287).
     if (c->reset_pending) {  // adder_hip_reset queued its memsets on the context's stream
         HIPCHK(c, hipStreamWaitEvent(stream, c->reset_e, 0));
         c->reset_pending = false;
@@ -1434,63 +1367,23 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
     if (c->sparse_mode)
         return fail(c, ADDER_E_BAD_PARAMS, "dense frames after sparse steps: the pixels' c_thresh and running_t have "
                     "diverged (pass every pixel as a sparse step, or adder_hip_reset)");
-    const bool collapse = c->p.multi_mode == ADDER_MULTI_COLLAPSE;
     const bool sticky_before = c->generic_sticky;
     const bool fpath = feature_path(c);
-
-    const bool generic = !c->continuous && (c->generic_sticky || c->perpx || feature_needs_perpx(c) ||
-                                            !(collapse && (float)c->p.delta_t_max <= time_spanned));
     if (fpath) {  // the corner test reads the running intensities (video.rs:736-744)
         c->running_enabled = true;
         int rc_ = prepare_feature_set(c, stream);
         if (rc_ != ADDER_OK) return rc_;
     }
-    const bool cb = generic && cb_possible(c, time_spanned);  // the bounded Collapse step instead of the generic one
-    if (!(time_spanned >= 1.0f) || time_spanned != (float)(uint32_t)time_spanned) c->frac_time_seen = true;
-    // constant runs: c_thresh is 0 now and cannot grow (c_thresh_max 0: crf 0), the time step is the one of every batch
-    // since the reset.  Once lost, the property stays lost until adder_hip_reset (a rolled-back batch included).
-    if (c->c_thresh != 0 || c->p.c_thresh_max != 0 || c->frac_time_seen || fpath || c->perpx ||
-        (c->cr_time != 0.0f && c->cr_time != time_spanned))
-        c->cr_valid = false;
-    c->cr_time = time_spanned;
-    const bool cr_off = env_flag("ADDER_HIP_NO_CR");  // (read per batch: the tests switch kernels inside one process)
-    const bool cr = cb && c->cr_valid && !cr_off;  // ... then only the roots are stepped (adder_cr_kernel)
-    // how long a run can be by now: frames since the reset in AbsoluteT (last_fired_t / T is an integer of that size), in DeltaT
-    // the bound the kernels' own reports keep down (AdderHipCtx::run_bound)
-    // (a batch that hands its records to the multi-GPU gather takes the bound every rank shares -- the frames since the reset:
-    // the kernels' reports follow each band's own content, a static band would leave the integer-state kernel where a busy one
-    // stays, and root expands ONE record kind per chunk)
-    const uint64_t run_frames = (c->p.time_mode == ADDER_TIME_ABSOLUTE_T || c->records_only)
-                                    ? c->frames_done : std::min<uint64_t>(c->run_bound, c->frames_done);
-    // run records (adder_rr_kernel): the same regime with integer state while n * 255 and n * time_spanned stay exact in
-    // binary32; AbsoluteT also wants last_fired_t on multiples of time_spanned (time_spanned == ref_time >= 255)
-    const bool rr_off = env_flag("ADDER_HIP_NO_RR");
-    // (Mode Normal under the same conditions runs it too -- adder_pixel.hpp rr_step; the other two kernels are Collapse's)
-    const bool rr_regime = cr || (generic && !collapse && c->cr_valid && rr_possible(c, time_spanned, true));
-    const bool rr = rr_regime && !rr_off &&
-                    (c->p.time_mode != ADDER_TIME_ABSOLUTE_T || (time_spanned == (float)c->p.ref_time && c->p.ref_time >= 255u)) &&
-                    (double)(run_frames + num_frames) * std::max(255.0, (double)time_spanned) < 16777216.0;
-    // lean runs (adder_lr_kernel): the lean regime in DeltaT under the same property, in blocked batches of events, while
-    // rho * 255 and rho * time_spanned stay exact in binary32 (rho <= frames since the reset)
-    const bool lr_off = env_flag("ADDER_HIP_NO_LR");
-    // (AbsoluteT: last_fired_t / T rides along as an integer when time_spanned == ref_time >= 255, like the run records')
-    const bool lr_time = c->p.time_mode == ADDER_TIME_DELTA_T ||
-                         (c->p.time_mode == ADDER_TIME_ABSOLUTE_T && time_spanned == (float)c->p.ref_time && c->p.ref_time >= 255u);
-    // (batches that hand their records out -- the multi-GPU gather -- run it too: the {rho, word} records are the smallest
-    // payload and root's expansion works the events out of them like the single-GPU one)
-    const bool lr = !generic && !c->continuous && collapse && lr_time && c->cr_valid && !lr_off &&
-                    launch_depth(c) > 1u && num_frames > 1u &&
-                    (double)(run_frames + num_frames) * std::max(255.0, (double)time_spanned) < 16777216.0;
-    // ... in packed bytes (adder_lp_kernel, four units per lane): DeltaT batches whose records the expansion reads itself
-    // (the pair's records lie in one run: the ring layout must keep a pair of segments adjacent)
-    const bool lp_off = env_flag("ADDER_HIP_NO_LP");
-    const bool lp = lr && !lp_off && c->p.time_mode == ADDER_TIME_DELTA_T && !c->records_only && park_group_shift_wanted() >= 1u;
-    const uint32_t variant = (lp ? 4096u : 0u) | ((lp && c->p.channels == 3) ? 8192u : 0u) | (collapse ? 1u : 0u) | (c->p.time_mode == ADDER_TIME_ABSOLUTE_T ? 2u : 0u) |
-                             (generic ? 4u : 0u) | (c->continuous ? 8u : 0u) |
-                             (c->n_units >= 4u ? 16u : 0u) |  // 16: the 4-units-per-lane one-frame kernel may run
-                             (cb ? 32u : 0u) | (cr ? 128u : 0u) | (lr ? 256u : 0u) | (rr ? 512u : 0u) | (c->wire_batch ? 1024u : 0u) |
-                             ((c->records_only && !lr) ? 64u : 0u);  // 64: lean records in per-segment logs (batches that hand them out)
+    BatchPlanIn in = plan_input(c, num_frames, time_spanned);
+    // (read per batch: the tests switch kernels inside one process)
+    in.no_lp = env_flag("ADDER_HIP_NO_LP"); in.no_lr = env_flag("ADDER_HIP_NO_LR");
+    in.no_rr = env_flag("ADDER_HIP_NO_RR"); in.no_cr = env_flag("ADDER_HIP_NO_CR");
+    const BatchPlan plan = plan_batch(in);
+    const uint32_t variant = plan.variant;
+    const bool generic = variant & kVarGeneric, lr = variant & kVarLeanRuns, rr = variant & kVarRunRecords;
+    c->frac_time_seen = plan.frac_time_seen; c->cr_valid = plan.cr_valid; c->cr_time = plan.cr_time;
     c->last_variant = variant;
+    if (plan.refused) return fail(c, ADDER_E_BAD_PARAMS, "%s", plan.refused);
     if (lr) {
         int rc_ = ensure_lr_tab(c, time_spanned, stream);
         if (rc_ != ADDER_OK) return rc_;
@@ -1505,25 +1398,12 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
         HIPCHK(c, dalloc(&c->d_rr_tab, tab.size()));
         HIPCHK(c, hipMemcpy(c->d_rr_tab, tab.data(), tab.size(), hipMemcpyHostToDevice));
     }
-    if (c->wire_batch && (c->continuous || fpath || c->records_only))
-        return fail(c, ADDER_E_BAD_PARAMS, "wire records straight from the expansion: dense FramePerfect batches without feature mode only "
-                    "(otherwise integrate events and serialise them with adder_hip_wire_events_device)");
-    if (c->records_only && (generic || c->continuous || fpath))
-        return fail(c, ADDER_E_BAD_PARAMS, "records can be handed out in the lean regime only (Collapse, delta_t_max <= "
-                    "time_spanned, no feature mode, no generic batch before): gather events instead");
-    if (generic) {
-        // per-event records go to a log per segment and chunk, sized by the hard bound of what a segment can emit
-        // (pop_top and a flush exclude each other in one frame when delta_t_max >= 2 * time: 2 instead of 3 per frame)
-        const bool two = collapse && (double)c->p.delta_t_max >= 2.0 * (double)time_spanned;
-        int rc_ = alloc_scratch(c, two ? AdderHipCtx::kScratchLog2 : AdderHipCtx::kScratchLog3);
-        if (rc_ == ADDER_OK) rc_ = alloc_deep_planes(c);
-        if (rc_ != ADDER_OK) return rc_;
-        c->generic_sticky = true;
-    } else if (!c->continuous) {
-        // (12-byte records in AbsoluteT, 8-byte ones otherwise: adder_pixel.hpp lean_decode8)
-        int rc_ = alloc_scratch(c, c->p.time_mode == ADDER_TIME_ABSOLUTE_T ? AdderHipCtx::kScratchLean : AdderHipCtx::kScratchLean8);
+    if (plan.scratch != kScratchNone) {
+        int rc_ = alloc_scratch(c, plan.scratch);
+        if (rc_ == ADDER_OK && generic) rc_ = alloc_deep_planes(c);
         if (rc_ != ADDER_OK) return rc_;
     }
+    c->generic_sticky = plan.generic_sticky;
     // an event buffer below the batch's worst case can overflow: keep an undo copy of the state so that the
     // overflow is recoverable (adder_hip_finish rolls back and reports the size needed)
     if (c->running_enabled && !c->running) {
@@ -1532,13 +1412,10 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     c->snap.valid = false;
-    {
-        const size_t per_frame = (size_t)c->n_units * (c->continuous ? c->max_depth + 3u : generic ? c->max_depth + 1u : 3u);
-        if (out_cap < per_frame * num_frames && !c->no_snapshot) {
-            int rc_ = take_snapshot(c, generic, stream);
-            if (rc_ != ADDER_OK) return rc_;
-            c->snap.generic_sticky = sticky_before;
-        }
+    if (out_cap < worst_case_events_per_frame(in) * num_frames && !c->no_snapshot) {
+        int rc_ = take_snapshot(c, generic, stream);
+        if (rc_ != ADDER_OK) return rc_;
+        c->snap.generic_sticky = sticky_before;
     }
     if (fpath) {
         int rc_ = prepare_per_unit_c_thresh(c, stream);
@@ -1569,7 +1446,7 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
     b.base.out = reinterpret_cast<AdderEventPod *>(d_out);
     b.base.out_cap = out_cap;
     b.base.frame_offsets = d_offsets;
-    b.base.lean = (variant & 512u) ? 3u : (generic || c->continuous) ? 0u : ((variant & 256u) ? 2u : 1u);  // 2: lean-runs records (lr_decode8), 3: run records (rr_event)
+    b.base.lean = plan.lean;
     b.base.abs_t = c->p.time_mode == ADDER_TIME_ABSOLUTE_T ? 1u : 0u;
     b.base.wire_rec = c->wire_batch ? (c->p.channels == 1 ? 9u : 11u) : 0u;
     b.base.sc = make_consts(c, time_spanned);
@@ -1579,10 +1456,10 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
     // run records: a fixed slot per (segment, frame) like the lean records' (at most one 8 / 12-byte record per unit and
     // frame), laid out by park_offset inside the log ring (2 KB per segment and frame there: enough) -- the expansion
     // reads the sixteen segments of a wave out of one contiguous stretch instead of sixteen logs 64 KB apart
-    const uint32_t pb = (variant & 512u) ? kWaveUnits * (c->p.time_mode == ADDER_TIME_ABSOLUTE_T ? 12u : 8u) : c->park_bytes;
+    const uint32_t pb = rr ? kWaveUnits * (c->p.time_mode == ADDER_TIME_ABSOLUTE_T ? 12u : 8u) : c->park_bytes;
     b.park_bytes = pb;
     // (a lean batch's region holds one record per unit and frame of the chunk: the same bytes as its fixed slots)
-    b.log_cap = (variant & 512u) ? 0u : (variant & 64u) ? kWaveUnits * c->chunk : c->log_cap;
+    b.log_cap = rr ? 0u : (variant & kVarLeanLog) ? kWaveUnits * c->chunk : c->log_cap;
     b.rr_tab = c->d_rr_tab;
     b.lr_tab = c->d_lr_tab;
     {
@@ -1595,24 +1472,9 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
     b.run_max = (lr || rr) ? c->d_run_max : nullptr;
     b.wofs_ring = c->wofs_ring;
     b.wcur = c->wcur;
-    // ring layout (park_offset): batches launched one frame at a time park frame-major, the others in groups of
-    // segments (ADDER_HIP_PARK_GROUP_SHIFT: 0 = segment-major)
-    if (b.log_cap) {
-        b.park_layout = ParkLayout{0u, 0u, 0u, 0u, 31u, 0xffffffffu};  // (unused: the records are appended to logs)
-    } else if (launch_depth(c) == 1u && (uint64_t)c->num_waves * pb <= 0xffffffffull) {
-        b.park_layout = ParkLayout{31u, 0u, c->num_waves * pb, pb, 31u, 0xffffffffu};
-    } else {
-        uint32_t sh = c->park_group_shift;
-        while (sh && ((c->num_waves & ((1u << sh) - 1u)) || ((uint64_t)c->chunk * pb << sh) > 0xffffffffull)) --sh;
-        b.park_layout = ParkLayout{sh, (c->chunk * pb) << sh, pb << sh, pb, 31u, 0xffffffffu};
-        // segment-major: rotate the frame slots by the segment's group of 16 (needs a power-of-two chunk)
-        static const bool rot_on = [] { const char *e = getenv("ADDER_HIP_PARK_ROT"); return !e || atoi(e) != 0; }();
-        if (rot_on && sh == 0u && c->chunk >= 2u && (c->chunk & (c->chunk - 1u)) == 0u &&
-            (uint64_t)c->chunk * pb <= 0xffffffffull) {
-            b.park_layout.rot_shift = 4u;
-            b.park_layout.rot_mask = c->chunk - 1u;
-        }
-    }
+    static_assert((1u << kParkGroupShift) % kExpandSegs == 0, "a group of segments must hold whole expansion waves");
+    if (!batch_park_layout(b.log_cap, launch_depth(c), c->num_waves, c->chunk, pb, &b.park_layout))
+        return fail(c, ADDER_E_HIP, "internal error: %u segments, %u frames of %u bytes: no group layout", c->num_waves, c->chunk, pb);
     b.wtot_ring = c->wtot_ring;
     b.wpref_ring = c->wpref_ring;
     b.ftot_ring = c->ftot_ring;
@@ -1641,8 +1503,6 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
         b.timeline = c->d_timeline;
     }
     // (frame_offsets[0] and the record count are started by the first chunk's offsets kernel: nothing to clear here)
-    static const bool dbg_memset = env_flag("ADDER_HIP_DBG_DESC_MEMSET");  // (tests/test_gpu_stress.py: round 5's arrangement, on purpose)
-    if (dbg_memset && c->d_rec_total) HIPCHK(c, hipMemsetAsync(c->d_rec_total, 0, 4, stream));
     if (reinterpret_cast<uint8_t *>(c->d_ftab) == reinterpret_cast<uint8_t *>(c->d_batch) + kBatchDescBytes &&
         reinterpret_cast<uint8_t *>(c->h_ftab) == reinterpret_cast<uint8_t *>(c->h_batch) + kBatchDescBytes) {
         HIPCHK(c, hipMemcpyAsync(c->d_batch, c->h_batch, kBatchDescBytes + num_frames * sizeof(FrameTab),
@@ -1794,10 +1654,11 @@ extern "C" int adder_hip_integrate_records_device(AdderHipCtx *c, const uint8_t 
     if (!stream) { int rc_ = join_null_stream(c); if (rc_ != ADDER_OK) return rc_; }
     // the scratch must exist before the chunk size is known
     {
-        int rc_ = alloc_scratch(c, c->p.time_mode == ADDER_TIME_ABSOLUTE_T ? AdderHipCtx::kScratchLean : AdderHipCtx::kScratchLean8);
+        int rc_ = alloc_scratch(c, c->p.time_mode == ADDER_TIME_ABSOLUTE_T ? kScratchLean : kScratchLean8);
         if (rc_ != ADDER_OK) return rc_;
     }
-    if (c->ring_chunks < 2 || num_frames > c->chunk)
+    static_assert(AdderHipCtx::ring_chunks >= 2, "a records batch is packed into the ring's second chunk");
+    if (num_frames > c->chunk)
         return fail(c, ADDER_E_BAD_PARAMS, "a records batch holds at most adder_hip_chunk_frames() = %u frames", c->chunk);
     c->records_only = true;
     const bool snap = c->no_snapshot;
@@ -1816,7 +1677,7 @@ extern "C" int adder_hip_integrate_records_device(AdderHipCtx *c, const uint8_t 
     const uint32_t cap = kWaveUnits * c->chunk;
     const size_t chunk_bytes = (size_t)c->num_waves * cap * rb;
     uint8_t *const packed = c->park_ring + chunk_bytes;
-    const bool runs = (c->last_variant & 256u) != 0u;  // adder_lr_kernel ran: {rho, word} records, frame-major packing
+    const bool runs = (c->last_variant & kVarLeanRuns) != 0u;  // adder_lr_kernel ran: {rho, word} records, frame-major packing
     if (runs) {
         HIPCHK(c, adder_launch_slot_pack(c->d_batch, num_frames, c->num_waves, rb, packed, chunk_bytes, c->status, s));
     } else {
@@ -1931,7 +1792,7 @@ static int expand_records_impl(AdderHipCtx *c, const AdderBandRecords *bands, ui
         HIPCHK(c, adder_launch_expand_bands(d_blk, (uint32_t)kBatchDescBytes, n_bands, nw, nf, abs_t ? 1u : 0u, s, runs ? 1u : 0u,
                                             wire ? 1u : 0u));
     } else {
-        const uint32_t variant = 1u | (abs_t ? 2u : 0u) | 64u | (runs ? 256u : 0u) | (wire ? 1024u : 0u);
+        const uint32_t variant = kVarCollapse | (abs_t ? kVarAbsT : 0u) | kVarLeanLog | (runs ? kVarLeanRuns : 0u) | (wire ? kVarWire : 0u);
         for (uint32_t r = 0; r < n_bands; ++r)
             HIPCHK(c, adder_launch_expand(reinterpret_cast<const BatchArgs *>(d_blk + (size_t)r * kBatchDescBytes), 0u, nf,
                                           bands[r].num_segments, variant, 0u, s));
@@ -2116,15 +1977,7 @@ extern "C" int adder_hip_debug_timeline(AdderHipCtx *c, unsigned long long *dst)
 
 extern "C" unsigned adder_hip_last_batch_kernel(const AdderHipCtx *c) {
     if (!c) return ADDER_KERNEL_LEAN;
-    const uint32_t v = c->last_variant;  // (the order of adder_launch_frame's tests)
-    if (v & 8u) return ADDER_KERNEL_CONTINUOUS;
-    if (v & 512u) return ADDER_KERNEL_RUN_RECORDS;
-    if (v & 128u) return ADDER_KERNEL_CONSTANT_RUNS;
-    if (v & 32u) return ADDER_KERNEL_BOUNDED;
-    if (v & 4u) return ADDER_KERNEL_GENERIC;
-    if (v & 4096u) return ADDER_KERNEL_LEAN_RUNS_PACKED;
-    if (v & 256u) return ADDER_KERNEL_LEAN_RUNS;
-    return ADDER_KERNEL_LEAN;
+    return variant_frame_kernel(c->last_variant);
 }
 extern "C" int adder_hip_launch_plan_settled(const AdderHipCtx *c) {
     if (!c) return 1;
@@ -2461,46 +2314,6 @@ static uint32_t wire_scatter_blocks(const AdderHipCtx *c) {
     return env ? env : c->num_cus * 2u;  // (sweep, 1080p e = 0.3: 64-128: 203, 256: 197, 512: 185, 1024: 189 us per frame)
 }
 
-struct RingTiming {  // ADDER_HIP_RING_TIMING=1: where adder_hip_frame_submit's host time goes (printed when the process ends)
-    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t n = 0;
-    ~RingTiming() {
-        if (n) fprintf(stderr, "[adder_hip] frame_submit host us per call over %llu calls: upload %.1f | in-event pair %.1f | enqueue (description copy + frame kernel) %.1f | frame-event pair %.1f | hand-over launch %.1f | done event %.1f\n",
-                       (unsigned long long)n, acc[0] / n, acc[1] / n, acc[2] / n, acc[3] / n, acc[4] / n, acc[5] / n);
-    }
-};
-static RingTiming g_ring_timing;
-// ADDER_HIP_RING_TIMING=2: the GPU side of the last frames on one clock -- timing events before / behind the upload, around the
-// frame kernel and behind the hand-over; adder_hip_destroy prints them relative to the first (us)
-struct RingGpuTimeline {
-    static constexpr int kFrames = 96, kPer = 5;
-    hipEvent_t ev[kFrames][kPer] = {};
-    uint64_t n = 0;
-    bool made = false;
-    void make() {
-        if (made) return;
-        for (auto &row : ev)
-            for (hipEvent_t &e : row) (void)hipEventCreate(&e);
-        made = true;
-    }
-    void report() {
-        if (!made || n < 24) return;
-        (void)hipDeviceSynchronize();
-        const uint64_t first = n > (uint64_t)kFrames ? n - kFrames : 0, from = n - 16;
-        hipEvent_t base = ev[from % kFrames][0];
-        fprintf(stderr, "[adder_hip] ring timeline, us from frame %llu's upload start: upload start, upload end, kernel start, kernel end, hand-over end\n", (unsigned long long)from);
-        (void)first;
-        for (uint64_t f = from; f < n; ++f) {
-            float t[kPer];
-            for (int k = 0; k < kPer; ++k) (void)hipEventElapsedTime(&t[k], base, ev[f % kFrames][k]);
-            fprintf(stderr, "  frame %llu: %8.1f %8.1f %8.1f %8.1f %8.1f\n", (unsigned long long)f, t[0] * 1e3f, t[1] * 1e3f, t[2] * 1e3f, t[3] * 1e3f, t[4] * 1e3f);
-        }
-        n = 0;
-    }
-};
-static RingGpuTimeline g_ring_tl;
-static void ring_timeline_report() { g_ring_tl.report(); }
-#define RING_T(k) do { if (ring_timing) { const auto t_ = std::chrono::steady_clock::now(); g_ring_timing.acc[k] += std::chrono::duration<double, std::micro>(t_ - rt_).count(); rt_ = t_; } } while (0)
 static int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_stride, float time_spanned,
                              AdderEvent *direct_out, size_t direct_cap) {
     if (c->poisoned) return fail(c, ADDER_E_POISONED, "context is poisoned by an earlier failure: %s", c->err.c_str());
@@ -2522,25 +2335,7 @@ static int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_st
                                    : frame_slot_events(c, time_spanned);
     int rc = frame_slot_prepare(c, fs, need, direct_out == nullptr);
     if (rc != ADDER_OK) return rc;
-    if (!c->out_s) {
-        if (const char *e = getenv("ADDER_HIP_RING_SKIP_STREAMS")) {  // (diagnostic: shifts where the ring's streams land among the runtime's hardware queues)
-            for (int k = 0; k < atoi(e); ++k) {
-                hipStream_t dummy = nullptr;
-                HIPCHK(c, hipStreamCreateWithFlags(&dummy, hipStreamNonBlocking));
-                c->dummy_streams.push_back(dummy);
-            }
-        }
-        if (const char *e = getenv("ADDER_HIP_RING_PRIO")) {  // (diagnostic: 1 = out_s, 2 = in_s, 3 = both as high-priority streams)
-            int lo_prio = 0, hi_prio = 0;
-            HIPCHK(c, hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
-            const int m = atoi(e);
-            if (m & 1) HIPCHK(c, hipStreamCreateWithPriority(&c->out_s, hipStreamNonBlocking, hi_prio));
-            if ((m & 2) && !c->in_s) HIPCHK(c, hipStreamCreateWithPriority(&c->in_s, hipStreamNonBlocking, hi_prio));
-            if (m & 4) HIPCHK(c, hipStreamCreateWithPriority(&c->out_s, hipStreamNonBlocking, lo_prio));
-            if ((m & 8) && !c->in_s) HIPCHK(c, hipStreamCreateWithPriority(&c->in_s, hipStreamNonBlocking, lo_prio));
-        }
-        if (!c->out_s) HIPCHK(c, hipStreamCreateWithFlags(&c->out_s, hipStreamNonBlocking));
-    }
+    if (!c->out_s) HIPCHK(c, hipStreamCreateWithFlags(&c->out_s, hipStreamNonBlocking));
     if (!c->frame_e) HIPCHK(c, hipEventCreateWithFlags(&c->frame_e, hipEventDisableTiming));
     // The ring's uploads go on a stream of their own, so that the next frame's 2 MB cross the link beside this frame's
     // kernels instead of behind them: 220 -> 84 us per 1080p frame at the default quality (sparse frames: real video).
@@ -2551,23 +2346,13 @@ static int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_st
     // buffer (adder_hip_integrate_wire_device's path, no hand-over pass) -- measured no better for sparse frames and
     // 5 % worse for dense ones (the byte stores at its waves' edges are single PCIe writes): off by default.
     static const bool direct_wire_on = env_flag("ADDER_HIP_RING_DIRECT_WIRE");
-    static const bool own_upload_off = env_flag("ADDER_HIP_RING_ONE_STREAM");
     const bool wire_direct = direct_wire_on && c->f_wire && !direct_out && !c->continuous && !feature_path(c);
-    const bool own_upload = !direct_out && !own_upload_off;
-    hipStream_t up = c->stream;
+    const bool own_upload = !direct_out;
+    hipStream_t up = c->stream, ring_out = c->out_s;
+    bool post_on_main = false;
     if (own_upload) {
-        static const bool upload_on_out = env_flag("ADDER_HIP_RING_UPLOAD_ON_OUT");  // (diagnostic: uploads share the hand-over's stream)
-        if (!c->in_s && upload_on_out) c->in_s = c->out_s;
         if (!c->in_s) HIPCHK(c, hipStreamCreateWithFlags(&c->in_s, hipStreamNonBlocking));
         if (!c->in_e) HIPCHK(c, hipEventCreateWithFlags(&c->in_e, hipEventDisableTiming));
-        up = c->in_s;
-    }
-    // the ring's stream arrangement for this frame (AdderHipCtx::RingCand): the chosen one, or the candidate being measured
-    static const bool ring_tune_off = env_flag("ADDER_HIP_RING_NO_TUNE");
-    static const bool post_on_main_env = env_flag("ADDER_HIP_RING_POST_ON_MAIN");
-    hipStream_t ring_out = c->out_s;
-    bool post_on_main = post_on_main_env;
-    if (own_upload && !ring_tune_off && !post_on_main_env) {
         if (c->ring_cands.empty()) {
             // the context's own pair, post-processing on the context's stream, and three more pairs -- a spare stream between
             // two pairs, so that the pairs sit at every offset of the runtime's round robin over its (four) hardware queues
@@ -2588,32 +2373,20 @@ static int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_st
             c->ring_win_frames = c->ring_win_waits = 0;
             c->ring_win_skip = 6;
         }
+        // the ring's stream arrangement for this frame (AdderHipCtx::RingCand): the chosen one, or the candidate being measured
         const AdderHipCtx::RingCand &rc_ = c->ring_cands[c->ring_chosen >= 0 ? c->ring_chosen : c->ring_cur];
         up = rc_.in_s;
         ring_out = rc_.out_s;
         post_on_main = rc_.post_on_main;
     }
-    static const bool ring_timing = env_flag("ADDER_HIP_RING_TIMING");
-    static const bool ring_tl = [] { const char *e = getenv("ADDER_HIP_RING_TIMING"); return e && atoi(e) == 2; }();
-    hipEvent_t *tl = nullptr;
-    if (ring_tl) {
-        g_ring_tl.make();
-        tl = g_ring_tl.ev[g_ring_tl.n % RingGpuTimeline::kFrames];
-        HIPCHK(c, hipEventRecord(tl[0], up));
-    }
-    auto rt_ = std::chrono::steady_clock::now();
     if (row_stride == rowlen)
         HIPCHK(c, hipMemcpyAsync(fs.d_frame, frame, c->n_units, hipMemcpyHostToDevice, up));
     else
         HIPCHK(c, hipMemcpy2DAsync(fs.d_frame, rowlen, frame, row_stride, rowlen, c->rows, hipMemcpyHostToDevice, up));
-    RING_T(0);
-    if (tl) HIPCHK(c, hipEventRecord(tl[1], up));
     if (own_upload) {
         HIPCHK(c, hipEventRecord(c->in_e, up));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->in_e, 0));
     }
-    RING_T(1);
-    if (tl) HIPCHK(c, hipEventRecord(tl[2], c->stream));
     // the slot's own batch description: the shared one may still be read by the copy engine for the frame before
     struct Swap {
         AdderHipCtx *c;
@@ -2638,9 +2411,7 @@ static int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_st
     // the next frame's kernel -- which needs this frame's pixel state and nothing else of it.  The per-frame path is bound
     // by the frames' GPU time in a row at the reference's default quality (kernel 29 us + scan / expansion / hand-over
     // 40 us per 1080p frame: 82 us sustained); side by side the period is the longer of the two.
-    // (ADDER_HIP_RING_NO_SPLIT=1: everything on one stream, eager, as before.)
-    static const bool ring_split_off = env_flag("ADDER_HIP_RING_NO_SPLIT");
-    const bool ring_graph = swap.graph && !ring_split_off;
+    const bool ring_graph = swap.graph;
     c->use_graph = false;   // (the context's captured graphs point at the shared description)
     struct SlotTag {
         AdderHipCtx *c;
@@ -2650,7 +2421,7 @@ static int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_st
     // (a ring chunk of scratch per frame slot -- its share of the frame totals must also hold the scan's tile sums, 2 words per
     // tile: planes beyond 16 384 segments with a chunk shortened by the memory budget keep the one-stream form)
     const uint32_t scan_tiles = (c->num_waves + kScanTileWaves - 1u) / kScanTileWaves;
-    c->frame_only = !ring_split_off && c->f_slots <= c->ring_chunks && c->chunk >= 2u && c->chunk >= 2u * scan_tiles;
+    c->frame_only = c->f_slots <= c->ring_chunks && c->chunk >= 2u && c->chunk >= 2u * scan_tiles;
     c->no_snapshot = true;  // frames behind this one are submitted before its outcome is known: no rollback
     fs.out = direct_out ? direct_out : fs.h_events;
     fs.out_cap = need;
@@ -2661,8 +2432,6 @@ static int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_st
         c->poisoned = true;
         return rc;
     }
-    RING_T(2);
-    if (tl) HIPCHK(c, hipEventRecord(tl[3], c->stream));
     // where the frame's scan / expansion / hand-over go: the ring's second stream (behind an event), or -- post_on_main -- the
     // context's own stream behind the frame kernel (no cross-stream dependency at all)
     hipStream_t post_s = post_on_main ? c->stream : ring_out;
@@ -2670,7 +2439,6 @@ static int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_st
         HIPCHK(c, hipEventRecord(c->frame_e, c->stream));
         HIPCHK(c, hipStreamWaitEvent(ring_out, c->frame_e, 0));
     }
-    RING_T(3);
     const bool wire = c->f_wire && !direct_out;
     fs.wire = wire;
     // the hand-over: wire scatter (9 / 11-byte records straight into the slot: 25 % fewer bytes over PCIe, and what the raw
@@ -2726,32 +2494,22 @@ static int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_st
             return rc;
         }
     }
-    RING_T(4);
     HIPCHK(c, hipEventRecord(fs.done, post_s));
-    RING_T(5);
-    if (tl) {
-        HIPCHK(c, hipEventRecord(tl[4], post_s));
-        g_ring_tl.n += 1;
-    }
-    if (ring_timing) g_ring_timing.n += 1;
     c->f_submitted += 1;
     return ADDER_OK;
 }
 
 // Waiting for a frame slot's `done` event: polled for a while before the thread is parked -- an event wait that parks wakes
 // up tens of microseconds late (adder_hip_finish spins on its result flag for the same reason), and at one frame per 60 us
-// that is a third of the period.  ADDER_HIP_RING_NO_SPIN=1: park at once.
+// that is a third of the period.
 static hipError_t wait_done_event(hipEvent_t e) {
-    static const bool no_spin = env_flag("ADDER_HIP_RING_NO_SPIN");
-    if (!no_spin) {
-        const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-        uint32_t polls = 0;
-        for (;;) {
-            const hipError_t q = hipEventQuery(e);
-            if (q == hipSuccess) return hipSuccess;
-            if (q != hipErrorNotReady) return q;
-            if ((++polls & 15u) == 0u && std::chrono::steady_clock::now() >= t_end) break;
-        }
+    const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
+    uint32_t polls = 0;
+    for (;;) {
+        const hipError_t q = hipEventQuery(e);
+        if (q == hipSuccess) return hipSuccess;
+        if (q != hipErrorNotReady) return q;
+        if ((++polls & 15u) == 0u && std::chrono::steady_clock::now() >= t_end) break;
     }
     return hipEventSynchronize(e);
 }

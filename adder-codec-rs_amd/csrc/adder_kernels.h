@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "adder_pixel.hpp"
+#include "adder_variant.hpp"
 
 namespace adder {
 
@@ -111,20 +112,6 @@ struct FrameArgs {
     uint32_t abs_t;       // TimeMode::AbsoluteT (record decoding)
     uint32_t wire_rec;    // 0: `out` takes 12-byte AdderEvents; 9 / 11: the raw sink's records (bytes, back to back), out_cap in records
     StepConsts sc;        // running_t / cth are filled per frame from the table
-};
-
-struct ParkLayout {
-    uint32_t group_shift;   // log2 of the segments per group (31: one group = frame-major)
-    uint32_t group_stride;  // bytes between consecutive groups
-    uint32_t frame_stride;  // bytes between consecutive frame slots of one segment
-    uint32_t seg_stride;    // bytes between consecutive segments inside a group
-    // Rotation of the frame slots (segment-major blocked layout only): segment s keeps frame slot fi at
-    // (fi + (s >> rot_shift)) & rot_mask.  Without it every wave of the chip is, at any moment, writing (frame kernel)
-    // or reading (expansion: all waves work on the same frame) addresses that agree in their low 17 bits -- which
-    // memory channels that hits is then left to how the hardware hashes the upper bits of wherever the ring happened
-    // to be mapped.  rot_shift >= 4 keeps the 16 segments of one expansion wave a constant stride apart.
-    // Off: rot_shift = 31, rot_mask = 0xffffffff.
-    uint32_t rot_shift, rot_mask;
 };
 
 constexpr uint32_t kScanTileWaves = ADDER_SCAN_TILE_WAVES;  // (a multiple of 4)
@@ -284,15 +271,14 @@ __device__ __forceinline__ FrameArgs frame_args(const BatchArgs *b, uint32_t f) 
 }  // namespace adder
 
 extern "C" {
-// variant = collapse | abs_t << 1 | generic << 2 | continuous << 3 (host copy of what BatchArgs holds) | the band
-// has >= 4 units << 4 | bounded Collapse step << 5 (with generic: the per-event record format)
+// variant: the kVar* bits of adder_variant.hpp (the frame kernel it runs: variant_frame_kernel)
 // K1: frames [f, f + nb) in one launch (nb > 1 = temporal blocking).  grid_cap (0 = none) bounds the number of
 // workgroups of the lean kernel / of the expansion: the workgroups then walk their work items, which leaves room
 // for the other kernel to be resident on the same CUs
 hipError_t adder_launch_frame(const adder::BatchArgs *b, uint32_t f, uint32_t nb, uint32_t variant,
                               uint32_t num_waves, uint32_t grid_cap, hipStream_t stream,
                               const adder::Lean1wArgs *wide);  // (host copy of the level-0 planes, or null)
-// the lean-runs step in packed bytes (adder_lp_kernels.hip; variant bit 4096): a wave per PAIR of segments
+// the lean-runs step in packed bytes (adder_lp_kernels.hip; kVarPacked): a wave per PAIR of segments
 hipError_t adder_launch_lp(const adder::BatchArgs *b, uint32_t f, uint32_t nb, uint32_t lazy, uint32_t num_waves,
                            uint32_t grid_cap, hipStream_t stream);
 // ... and its expansion (adder_lpx_kernel): rec = 9 / 11 (the raw sink's records) or 12 (AdderEvents)

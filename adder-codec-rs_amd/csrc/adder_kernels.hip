@@ -788,23 +788,20 @@ __device__ __forceinline__ void lr_frames(const BatchArgs *__restrict__ b, const
             i += gn;  // (wt of these frames stays 0)
             continue;
         }
-        // (REENTER: one staged group per trip; otherwise the rest of the launch, staging as it goes)
-        const uint32_t i_first = i;
-        const uint32_t i_end = 1 ? (i + kLrGroup < nb ? i + kLrGroup : nb) : nb;
+        // one staged group per trip
+        const uint32_t i_end = i + kLrGroup < nb ? i + kLrGroup : nb;
 #pragma clang loop unroll(disable)
         for (; i + 2u <= i_end; i += 2u) {
-            if (!1 && (i % kLrGroup) == 0u && i != i_first) stage(i);
             uint32_t k0 = 0u, k1 = 0u;
             uint32_t t0 = frame(i, k0);
             uint32_t t1 = frame(i + 1u, k1);
-            if (1) last_recs = t1 >> 16;
+            last_recs = t1 >> 16;
             const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan_dpp(k0 | (k1 << 16)), kWave - 1);
             t0 |= tot & 0xffffu;
             t1 |= tot >> 16;
             wt = lane == i ? t0 : lane == i + 1u ? t1 : wt;
         }
         if (i < i_end) {  // (the launch's last frame, odd launches only)
-            if (!1 && (i % kLrGroup) == 0u && i != i_first) stage(i);
             uint32_t k0 = 0u;
             uint32_t t0 = frame(i, k0);
             t0 |= (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan_dpp(k0), kWave - 1);
@@ -1513,7 +1510,7 @@ __device__ __forceinline__ void cb_run_segment(const BatchArgs *__restrict__ b, 
                         cb_stage_issue<FULL>(fr0, n_units_u, sgw, u0, lane, i, nb, w.in, direct);
                     }
                     __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the group has landed
-                    pref = 1 != 0 && i + kCbInFrames < nb;
+                    pref = i + kCbInFrames < nb;
                     if (pref) cb_stage_issue<FULL>(fr0, n_units_u, sgw, u0, lane, i + kCbInFrames, nb, cur ? w.in : buf_b, direct);
                     cur_in = reinterpret_cast<const InT *>(cur ? buf_b : w.in) + lane;
 #if ADDER_CB_QUIET_GROUPS
@@ -3620,33 +3617,34 @@ extern "C" hipError_t adder_launch_divtest(unsigned long long *d_bad, hipStream_
 extern "C" hipError_t adder_launch_frame(const BatchArgs *b, uint32_t f, uint32_t nb, uint32_t variant,
                                          uint32_t num_waves, uint32_t grid_cap, hipStream_t stream,
                                          const Lean1wArgs *wide) {
-    const bool collapse = variant & 1u, abs_t = variant & 2u, generic = variant & 4u;
+    const bool collapse = variant & kVarCollapse, abs_t = variant & kVarAbsT;
+    const uint32_t lazy = (variant & kVarLazyState) ? 1u : 0u;  // (more launches of this batch follow: variant_lazy_state_bit)
     const uint32_t S = (num_waves + kWavesPerBlock - 1) / kWavesPerBlock;  // step workgroups
-    if (variant & 8u) {  // Mode::Continuous
+    const unsigned kernel = variant_frame_kernel(variant);
+    if (kernel == ADDER_KERNEL_CONTINUOUS) {
         if (abs_t) hipLaunchKernelGGL((adder_cont_kernel<true>), dim3(S), dim3(kBlockThreads), 0, stream, b, f, nb);
         else hipLaunchKernelGGL((adder_cont_kernel<false>), dim3(S), dim3(kBlockThreads), 0, stream, b, f, nb);
         return hipGetLastError();
     }
-    if (variant & 512u) {  // run records (the bounded Collapse regime at c_thresh 0, integer state)
+    if (kernel == ADDER_KERNEL_RUN_RECORDS) {  // (the bounded Collapse regime at c_thresh 0, integer state)
         const uint32_t SG = grid_cap && grid_cap < S ? grid_cap : S;
-        const uint32_t lazy = (variant & 2048u) ? 1u : 0u;  // (more launches of this batch follow: adder_hip_api.cpp lazy_state_bit)
         if (abs_t) hipLaunchKernelGGL((adder_rr_kernel<true>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb, lazy);
         else hipLaunchKernelGGL((adder_rr_kernel<false>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb, lazy);
         return hipGetLastError();
     }
-    if (variant & 128u) {  // constant runs (the bounded Collapse regime at c_thresh 0)
+    if (kernel == ADDER_KERNEL_CONSTANT_RUNS) {  // (the bounded Collapse regime at c_thresh 0)
         const uint32_t SG = grid_cap && grid_cap < S ? grid_cap : S;
         if (abs_t) hipLaunchKernelGGL((adder_cr_kernel<true>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb);
         else hipLaunchKernelGGL((adder_cr_kernel<false>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb);
         return hipGetLastError();
     }
-    if (variant & 32u) {  // bounded Collapse step
+    if (kernel == ADDER_KERNEL_BOUNDED) {
         const uint32_t SG = grid_cap && grid_cap < S ? grid_cap : S;
         if (abs_t) hipLaunchKernelGGL((adder_cb_kernel<true>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb);
         else hipLaunchKernelGGL((adder_cb_kernel<false>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb);
         return hipGetLastError();
     }
-    if (generic) {
+    if (kernel == ADDER_KERNEL_GENERIC) {
         const uint32_t SG = grid_cap && grid_cap < S ? grid_cap : S;
         if (collapse) {
             if (abs_t) hipLaunchKernelGGL((adder_frame_kernel<true, true>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb);
@@ -3658,18 +3656,17 @@ extern "C" hipError_t adder_launch_frame(const BatchArgs *b, uint32_t f, uint32_
         return hipGetLastError();
     }
     if (!collapse) return hipErrorInvalidValue;  // the lean step is Collapse-only
-    if (variant & 4096u)  // lean runs, packed bytes (adder_lp_kernels.hip): DeltaT batches of events or wire records
-        return adder_launch_lp(b, f, nb, (variant & 2048u) ? 1u : 0u, num_waves, grid_cap, stream);
-    if (variant & 256u) {  // lean runs (DeltaT, constant runs): every launch of the batch, whatever its length
+    if (kernel == ADDER_KERNEL_LEAN_RUNS_PACKED)  // (adder_lp_kernels.hip): DeltaT batches of events or wire records
+        return adder_launch_lp(b, f, nb, lazy, num_waves, grid_cap, stream);
+    if (kernel == ADDER_KERNEL_LEAN_RUNS) {  // (DeltaT, constant runs): every launch of the batch, whatever its length
         const uint32_t SR = grid_cap && grid_cap < S ? grid_cap : S;
-        const uint32_t lazy = (variant & 2048u) ? 1u : 0u;  // (more launches of this batch follow: adder_hip_api.cpp lazy_state_bit)
         if (abs_t) hipLaunchKernelGGL((adder_lr_kernel<true>), dim3(SR), dim3(kBlockThreads), 0, stream, b, f, nb, lazy);
         else hipLaunchKernelGGL((adder_lr_kernel<false>), dim3(SR), dim3(kBlockThreads), 0, stream, b, f, nb, lazy);
         return hipGetLastError();
     }
 #if ADDER_UNITS_PER_LANE == 2 && ADDER_LEAN1_WIDE
-    const bool lean_log = variant & 64u;  // blocked batches: records in per-segment logs (every launch, also a chunk's 1-frame tail)
-    if (nb == 1u && !lean_log && num_waves % 2u == 0u && (variant & 16u) && wide) {
+    const bool lean_log = variant & kVarLeanLog;  // blocked batches: records in per-segment logs (every launch, also a chunk's 1-frame tail)
+    if (nb == 1u && !lean_log && num_waves % 2u == 0u && (variant & kVarWide) && wide) {
         const uint32_t waves = (num_waves / 2u + kLean1wPairs - 1u) / kLean1wPairs;
         const uint32_t grid = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
         if (abs_t) hipLaunchKernelGGL((adder_lean1w_kernel<true>), dim3(grid), dim3(kBlockThreads), 0, stream, b, f, *wide);
@@ -3745,25 +3742,26 @@ extern "C" hipError_t adder_launch_expand(const BatchArgs *b, uint32_t f0, uint3
     uint32_t total = xblocks * nf;
     if (grid_cap && grid_cap < total) total = grid_cap;
     const dim3 grid(total);
-    const bool abs_t = variant & 2u, generic = variant & 4u, continuous = variant & 8u, wire = variant & 1024u;
+    const bool abs_t = variant & kVarAbsT, generic = variant & kVarGeneric, continuous = variant & kVarContinuous;
+    const bool wire = variant & kVarWire, lean_log = variant & kVarLeanLog, lean_runs = variant & kVarLeanRuns;
 #define ADDER_X(F, A, W) hipLaunchKernelGGL((adder_expand_kernel<F, A, W>), grid, dim3(kBlockThreads), 0, stream, b, f0, xblocks, nf, items)
 #define ADDER_XW(F, A) do { if (wire) ADDER_X(F, A, true); else ADDER_X(F, A, false); } while (0)
     if (continuous) ADDER_X(2, false, false);  // (its events are stored as they are decoded: no wire form)
-    else if (variant & 512u) {  // run records in per-segment logs
+    else if (variant & kVarRunRecords) {  // run records in per-segment logs
         if (abs_t) ADDER_XW(4, true);
         else ADDER_XW(4, false);
-    } else if (generic && (variant & 32u)) ADDER_XW(0, true);
+    } else if (generic && (variant & kVarBounded)) ADDER_XW(0, true);
     else if (generic) ADDER_XW(0, false);
-    else if ((variant & 64u) && (variant & 256u)) {  // lean-runs records found through a run table (a band's packed records on root)
+    else if (lean_log && lean_runs) {  // lean-runs records found through a run table (a band's packed records on root)
         if (abs_t) ADDER_XW(6, true);
         else ADDER_XW(6, false);
-    } else if (variant & 64u) {
+    } else if (lean_log) {
         if (abs_t) ADDER_XW(3, true);
         else ADDER_XW(3, false);
-    } else if (variant & 4096u) {  // adder_lp_kernel's records (DeltaT): the expansion of adder_lp_kernels.hip
+    } else if (variant & kVarPacked) {  // adder_lp_kernel's records (DeltaT): the expansion of adder_lp_kernels.hip
         if (host_b == nullptr || f0 % host_b->chunk != 0u || nf > host_b->chunk) return hipErrorInvalidValue;  // (a launch covers frames of one chunk)
-        return adder_launch_lpx(b, host_b, f0, nf, wire ? ((variant & 8192u) ? 11u : 9u) : 12u, stream);
-    } else if (variant & 256u) {
+        return adder_launch_lpx(b, host_b, f0, nf, wire ? ((variant & kVarPackedRgb) ? 11u : 9u) : 12u, stream);
+    } else if (lean_runs) {
         if (abs_t) ADDER_XW(5, true);
         else ADDER_XW(5, false);
     } else if (abs_t) ADDER_XW(1, true);
