@@ -16,14 +16,16 @@ from ._native import (  # noqa: F401
 from .video import CRF, crf_feature_radius, HipVideo, raw_header, raw_events, raw_eof, synth_clip_device  # noqa: F401
 from .framer import HipFramer, contiguous_run_segments, FRAMED_U8, DVS, FRAME_U8, FRAME_U16, FRAME_U32  # noqa: F401
 from .compressed import CompressedEncoder, compressed_decode  # noqa: F401
-from .quality import calculate_quality_metrics, calculate_mse, calculate_psnr  # noqa: F401
+from .quality import calculate_quality_metrics, calculate_mse, calculate_psnr, HipQuality  # noqa: F401
+from . import quality as _quality
 from . import dvs as _dvs
 from .dvs import HipDvs, adder_to_dvs_file, DVS_EVENT_DTYPE, DAT_DTYPE  # noqa: F401
 
 
 def load():
-    """Loads libadder_hip.so and binds every symbol include/adder_hip.h, adder_framer.h, adder_compressed.h and
-    adder_dvs.h declare; raises if one is missing."""
+    """Loads libadder_hip.so and binds every symbol include/adder_hip.h, adder_framer.h, adder_compressed.h,
+    adder_dvs.h and adder_quality.h declare; raises if one is missing."""
     L = _native.load()
     _dvs.load()
+    _quality.load()
     return L

@@ -162,6 +162,7 @@ SYMBOLS = {
     "adder_hip_chunk_offsets_device": (_i32, [_vp, _vp, _sz, _vp, _vp]),
     "adder_hip_running_intensities": (_i32, [_vp, _vp]),
     "adder_hip_enable_running_intensities": (_i32, [_vp, _i32]),
+    "adder_hip_running_intensities_device": (_i32, [_vp, _vp, _vp]),
     "adder_hip_last_batch_ms": (_f32, [_vp]),
     "adder_hip_launch_plan_settled": (_i32, [_vp]),
     "adder_hip_last_batch_kernel": (_u32, [_vp]),

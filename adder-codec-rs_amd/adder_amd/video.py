@@ -149,6 +149,14 @@ class HipVideo:
         N.check(self.h, self.L.adder_hip_running_intensities(self.h, out.ctypes.data))
         return out.reshape(self.rows, self.width, self.channels)
 
+    def running_intensities_device(self, d_out, stream=None):
+        """The same plane into the uint8 CUDA tensor d_out (n_units bytes), queued on `stream` behind every batch of this
+        context, without a host synchronisation (adder_hip_running_intensities_device)."""
+        assert d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= self.n_units
+        N.check(self.h, self.L.adder_hip_running_intensities_device(self.h, d_out.data_ptr(),
+                                                                     C.c_void_p(stream) if stream else None))
+        return d_out
+
     # ---- host-buffer entry points --------------------------------------------------------
     def _host_out(self, cap):
         """Event buffer in page-locked host memory (PCIe copies at link speed)."""

@@ -133,6 +133,9 @@ struct AdderHipCtx {
     BatchResult *h_result = nullptr;  // pinned: adder_publish_kernel writes it, finish() reads it
     hipEvent_t reset_e = nullptr;     // adder_hip_reset's memsets (queued on the context's stream, not waited for)
     bool reset_pending = false;
+    // adder_hip_running_intensities_device's copy of the plane, on the caller's stream: what writes the plane next waits
+    hipEvent_t ri_copy_e = nullptr, ri_src_e = nullptr;
+    bool ri_copy_pending = false;
     size_t ftab_cap = 0;            // entries
     // capture streams/events and the cache of instantiated frame-loop graphs
     hipStream_t cap_s = nullptr, cap_s2 = nullptr;
@@ -376,6 +379,8 @@ static void free_ctx(AdderHipCtx *c) {
     if (c->h_desc) (void)hipHostFree(c->h_desc);
     if (c->h_result) (void)hipHostFree(c->h_result);
     if (c->reset_e) (void)hipEventDestroy(c->reset_e);
+    if (c->ri_copy_e) (void)hipEventDestroy(c->ri_copy_e);
+    if (c->ri_src_e) (void)hipEventDestroy(c->ri_src_e);
     for (hipEvent_t e : {c->cap_e1, c->cap_e2[0], c->cap_e2[1], c->cap_e2[2], c->cap_e2[3], c->cap_e2[4]})
         if (e) (void)hipEventDestroy(e);
     if (c->cap_s) (void)hipStreamDestroy(c->cap_s);
@@ -723,6 +728,15 @@ extern "C" int adder_hip_reset_c_thresh(AdderHipCtx *c, uint8_t baseline) {
         HIPCHK(c, hipMemsetAsync(c->cth_px, baseline, c->n_pad, c->stream));
         HIPCHK(c, hipMemsetAsync(c->cctr_px, 0, c->n_pad, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return ADDER_OK;
+}
+
+// a device copy of the running-intensities plane may still be reading it on the caller's stream
+static int join_ri_copy(AdderHipCtx *c, hipStream_t s) {
+    if (c->ri_copy_pending) {
+        HIPCHK(c, hipStreamWaitEvent(s, c->ri_copy_e, 0));
+        c->ri_copy_pending = false;
     }
     return ADDER_OK;
 }
@@ -1364,6 +1378,7 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
         HIPCHK(c, hipStreamWaitEvent(stream, c->reset_e, 0));
         c->reset_pending = false;
     }
+    { int rc_ = join_ri_copy(c, stream); if (rc_ != ADDER_OK) return rc_; }
     if (c->sparse_mode)
         return fail(c, ADDER_E_BAD_PARAMS, "dense frames after sparse steps: the pixels' c_thresh and running_t have "
                     "diverged (pass every pixel as a sparse step, or adder_hip_reset)");
@@ -2018,6 +2033,7 @@ extern "C" int adder_hip_reset(AdderHipCtx *c) {
     if (c->f_submitted != c->f_collected || c->submitted != c->collected)
         return fail(c, ADDER_E_BAD_PARAMS, "frames are in flight (collect them first)");
     HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = join_ri_copy(c, c->stream); if (rc_ != ADDER_OK) return rc_; }
     int rc = init_state(c);
     if (rc != ADDER_OK) return rc;
     // the memsets are queued on the context's stream; whoever touches the state next orders itself behind them
@@ -2748,6 +2764,7 @@ extern "C" int adder_hip_integrate_sparse_device(AdderHipCtx *c, const AdderSpar
         HIPCHK(c, hipStreamWaitEvent(s, c->reset_e, 0));
         c->reset_pending = false;
     }
+    { int rc_ = join_ri_copy(c, s); if (rc_ != ADDER_OK) return rc_; }
     int rc = sparse_prepare(c, n, s);
     if (rc != ADDER_OK) return rc;
     if (c->running_enabled && !c->running) {
@@ -2830,6 +2847,31 @@ extern "C" int adder_hip_running_intensities(AdderHipCtx *c, uint8_t *dst) {
     }
     { int rc_ = settle_reset(c); if (rc_ != ADDER_OK) return rc_; }
     HIPCHK(c, hipMemcpy(dst, c->running, c->n_units, hipMemcpyDeviceToHost));
+    return ADDER_OK;
+}
+
+extern "C" int adder_hip_running_intensities_device(AdderHipCtx *c, uint8_t *d_dst, void *stream) {
+    if (!c || !d_dst) return ADDER_E_BAD_PARAMS;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!c->running) {  // never enabled before a batch: the plane is still all zeros
+        HIPCHK(c, hipMemsetAsync(d_dst, 0, c->n_units, s));
+        return ADDER_OK;
+    }
+    if (!c->ri_copy_e) HIPCHK(c, hipEventCreateWithFlags(&c->ri_copy_e, hipEventDisableTiming));
+    if (!c->ri_src_e) HIPCHK(c, hipEventCreateWithFlags(&c->ri_src_e, hipEventDisableTiming));
+    // behind every batch: the host-pointer forms and adder_hip_reset's memsets queue on the context's stream; a device
+    // batch on the caller's stream is the last one (the next needs adder_hip_finish, which waits for it) and may still
+    // be in flight
+    HIPCHK(c, hipEventRecord(c->ri_src_e, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(s, c->ri_src_e, 0));
+    if (c->pending_stream && c->pending_stream != c->stream && c->pending_stream != s) {
+        HIPCHK(c, hipEventRecord(c->ri_src_e, c->pending_stream));
+        HIPCHK(c, hipStreamWaitEvent(s, c->ri_src_e, 0));
+    }
+    HIPCHK(c, hipMemcpyAsync(d_dst, c->running, c->n_units, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipEventRecord(c->ri_copy_e, s));
+    c->ri_copy_pending = true;
     return ADDER_OK;
 }
 

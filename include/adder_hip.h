@@ -280,6 +280,12 @@ int adder_hip_chunk_offsets_device(AdderHipCtx *ctx, const AdderEvent *d_events,
  * band's [rows][width][channels] u8 plane to a host buffer. */
 int adder_hip_running_intensities(AdderHipCtx *ctx, uint8_t *dst_host);
 int adder_hip_enable_running_intensities(AdderHipCtx *ctx, int enable);
+/* The same plane into device memory (n_units bytes at d_dst), queued on `stream` (NULL: the default stream) behind
+ * every batch the context has queued, on whichever stream it ran, with no host synchronisation -- the input of
+ * include/adder_quality.h's metrics (the viewer's input frame vs running intensities).  All zeros if the plane was
+ * never enabled before a batch; a pending adder_hip_reset is applied first.  The context's next batch or reset waits
+ * for the copy. */
+int adder_hip_running_intensities_device(AdderHipCtx *ctx, uint8_t *d_dst, void *stream);
 
 /* Duration in milliseconds of the kernels of the last adder_hip_integrate_device
  * batch, measured with HIP events on the launch stream (0 if none). */
