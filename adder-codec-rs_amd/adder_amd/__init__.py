@@ -20,12 +20,15 @@ from .quality import calculate_quality_metrics, calculate_mse, calculate_psnr, H
 from . import quality as _quality
 from . import dvs as _dvs
 from .dvs import HipDvs, adder_to_dvs_file, DVS_EVENT_DTYPE, DAT_DTYPE  # noqa: F401
+from . import prophesee as _prophesee
+from .prophesee import HipProphesee, prophesee_to_adder_file  # noqa: F401
 
 
 def load():
     """Loads libadder_hip.so and binds every symbol include/adder_hip.h, adder_framer.h, adder_compressed.h,
-    adder_dvs.h and adder_quality.h declare; raises if one is missing."""
+    adder_dvs.h, adder_quality.h and adder_prophesee.h declare; raises if one is missing."""
     L = _native.load()
     _dvs.load()
+    _prophesee.load()
     _quality.load()
     return L
