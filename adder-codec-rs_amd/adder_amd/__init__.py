@@ -22,13 +22,16 @@ from . import dvs as _dvs
 from .dvs import HipDvs, adder_to_dvs_file, DVS_EVENT_DTYPE, DAT_DTYPE  # noqa: F401
 from . import prophesee as _prophesee
 from .prophesee import HipProphesee, prophesee_to_adder_file  # noqa: F401
+from . import stream_tools as _stream_tools
+from .stream_tools import HipStreamMigrator, HipStreamInfo, migrate_file, adder_info_file  # noqa: F401
 
 
 def load():
     """Loads libadder_hip.so and binds every symbol include/adder_hip.h, adder_framer.h, adder_compressed.h,
-    adder_dvs.h, adder_quality.h and adder_prophesee.h declare; raises if one is missing."""
+    adder_dvs.h, adder_quality.h, adder_prophesee.h and adder_stream.h declare; raises if one is missing."""
     L = _native.load()
     _dvs.load()
     _prophesee.load()
     _quality.load()
+    _stream_tools.load()
     return L

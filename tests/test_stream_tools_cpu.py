@@ -1,0 +1,353 @@
+"""Stream migration and adder-info (include/adder_stream.h) without a GPU: known answers that pin the restatement
+(tests/stream_tools_oracle.py) -- the reference's own test vectors, the goldens, hand-made streams for every arm of
+the dynamic-range fold -- and the host helpers of the C-ABI: header rewrite, report text, symbol table, no fallback."""
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import adder_stream_np as S
+import stream_tools_oracle as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+GOLDENS = ["adder_info_test_sample.adder", "bunny_v2_dt.adder", "bunny_v2_t.adder", "nyc_v1_1px.adder",
+           "nyc_source_v2_2_1px.adder", "sample_3_ordered.adder", "sample_3_unordered.adder", "virat_small_gray.adder"]
+NONE = 0xFF
+DVS_CAM = 6
+
+
+def golden_bytes(name):
+    return open(os.path.join(GOLDEN, name), "rb").read()
+
+
+def meta_of(w=1, h=1, ch=1, version=2, time_mode=0, ref=255, cam=0, tps=7650, dtm=2550):
+    return dict(width=w, height=h, channels=ch, version=version, time_mode=time_mode, ref_interval=ref,
+                source_camera=cam, tps=tps, delta_t_max=dtm, adu_interval=0)
+
+
+def times(out):
+    return [e[4] for e in out]
+
+
+def ev1(d, t, x=0):
+    return (x, 0, NONE, d, t)
+
+
+# ---- migration --------------------------------------------------------------------------------------------------
+
+def test_reference_test_migrate_v2():
+    """stream_migration.rs::test_migrate_v2: v1, FramedU8, ref 255"""
+    out, bad = R.Migration(meta_of(version=1), R.ABSOLUTE_T).run([ev1(5, 600), ev1(5, 600), ev1(5, 600), ev1(5, 123)])
+    assert bad is None and times(out) == [600, 1365, 2130, 2418]
+    assert [e[:4] for e in out] == [(0, 0, NONE, 5)] * 4
+
+
+def test_v0_and_unframed_streams_are_not_rounded_up():
+    ev = [ev1(5, 600), ev1(5, 600), ev1(5, 123)]
+    assert times(R.Migration(meta_of(version=0), R.ABSOLUTE_T).run(ev)[0]) == [600, 1200, 1323]
+    assert times(R.Migration(meta_of(version=2, cam=DVS_CAM), R.ABSOLUTE_T).run(ev)[0]) == [600, 1200, 1323]
+    # a time on the grid stays: 510 % 255 == 0
+    assert times(R.Migration(meta_of(), R.ABSOLUTE_T).run([ev1(5, 510), ev1(5, 1)])[0]) == [510, 511]
+
+
+def test_other_output_modes_pass_events_through():
+    ev = [ev1(5, 600), ev1(255, 7), ev1(5, 600)]
+    for meta, out_mode in ((meta_of(), R.DELTA_T), (meta_of(), R.MIXED), (meta_of(time_mode=1), R.ABSOLUTE_T),
+                           (meta_of(time_mode=2), R.DELTA_T)):
+        assert R.Migration(meta, out_mode).run(ev) == (ev, None)
+
+
+def test_d_empty_adds_its_time_like_any_other():
+    out, _ = R.Migration(meta_of(), R.ABSOLUTE_T).run([ev1(5, 100), ev1(255, 255), ev1(5, 10)])
+    assert times(out) == [100, 510, 520]
+
+
+def test_inverse_is_the_conditional_round_up():
+    out, bad = R.Migration(meta_of(time_mode=1), R.DELTA_T).run([ev1(5, 600), ev1(5, 1365), ev1(5, 2130), ev1(5, 2418)])
+    assert bad is None and times(out) == [600, 600, 600, 123]
+    out, _ = R.Migration(meta_of(time_mode=1), R.DELTA_T).run([ev1(5, 510), ev1(5, 511)])
+    assert times(out) == [510, 1]
+    out, _ = R.Migration(meta_of(time_mode=1, cam=DVS_CAM), R.DELTA_T).run([ev1(5, 600), ev1(5, 700)])
+    assert times(out) == [600, 100]
+
+
+def test_migration_errors():
+    big = (1 << 32) - 10
+    out, bad = R.Migration(meta_of(w=2), R.ABSOLUTE_T).run([ev1(5, big), ev1(5, 3, x=1), ev1(5, 9), ev1(5, 1)])
+    assert bad == 2 and times(out) == [big, 3]  # (2^32 - 10) rounded up to the grid, + 9: above u32::MAX
+    # ref 255 rounds 2^32 - 10 up to u32::MAX exactly; ref 5000 rounds it past 2^32, and then the unit's next event
+    # is the bad one whatever its t
+    out, bad = R.Migration(meta_of(w=2), R.ABSOLUTE_T).run([ev1(5, big), ev1(5, 3, x=1), ev1(5, 0)])
+    assert bad is None and times(out) == [big, 3, (1 << 32) - 1]
+    out, bad = R.Migration(meta_of(w=2, ref=5000), R.ABSOLUTE_T).run([ev1(5, big), ev1(5, 3, x=1), ev1(5, 0)])
+    assert bad == 2 and times(out) == [big, 3]
+    out, bad = R.Migration(meta_of(w=2, cam=DVS_CAM), R.ABSOLUTE_T).run([ev1(5, big), ev1(5, 9), ev1(5, 1)])
+    assert bad == 2 and times(out) == [big, big + 9]
+    out, bad = R.Migration(meta_of(time_mode=1), R.DELTA_T).run([ev1(5, 600), ev1(5, 764)])
+    assert bad == 1 and times(out) == [600]  # 764 < 765
+    assert R.Migration(meta_of(), R.ABSOLUTE_T).run([ev1(5, 1), ev1(5, 1, x=1)])[1] == 1  # outside the plane
+
+
+def test_nyc_golden_pair_byte_for_byte():
+    src, want = golden_bytes("nyc_v1_1px.adder"), golden_bytes("nyc_source_v2_2_1px.adder")
+    meta, ev, _ = S.read_adder(src)
+    assert meta["version"] == 1 and len(ev) == 5
+    out, bad = R.Migration(meta, R.ABSOLUTE_T).run(ev)
+    assert bad is None
+    got = R.migrated_header(src, R.ABSOLUTE_T)
+    assert got == want[:33]
+    mig = np.zeros(5, S.EVENT_DTYPE)
+    for k, e in enumerate(out):
+        mig[k] = (e[0], e[1], e[2], e[3], 0, e[4])
+    body = S.write_adder(dict(meta, version=2, time_mode=1), mig, close=False)[33:]
+    assert body == want[33:33 + 5 * 9]  # the golden ends in the old 9-byte end marker, ours in the 11-byte one
+
+
+def test_bunny_pair_agrees_in_329_of_333_times():
+    """the reference's test_migrate_v2_bunny_1px rounds up unconditionally; migrate_v2 and our transcoder do not"""
+    meta_t, ev_t, _ = S.read_adder(golden_bytes("bunny_v2_t.adder"))
+    meta_dt, ev_dt, _ = S.read_adder(golden_bytes("bunny_v2_dt.adder"))
+    assert (len(ev_t), len(ev_dt)) == (1117, 333) and meta_t["time_mode"] == 1 and meta_dt["time_mode"] == 0
+    out, bad = R.Migration(meta_t, R.DELTA_T).run(ev_t[:333])
+    assert bad is None
+    for f, k in (("x", 0), ("y", 1), ("d", 3)):
+        assert [e[k] for e in out] == ev_dt[f].tolist()
+    diff = [k for k in range(333) if out[k][4] != int(ev_dt["t"][k])]
+    assert len(diff) == 4
+    ref = meta_t["ref_interval"]
+    assert all(int(ev_t["t"][k - 1]) % ref == 0 for k in diff)  # a 1x1 plane: the predecessor is the event before
+    # with the unconditional rule of that test they all agree
+    last, uncond = 0, []
+    for t in ev_t["t"][:333].tolist():
+        uncond.append(t - last)
+        last = (t // ref + 1) * ref
+    assert uncond == ev_dt["t"].tolist()
+
+
+def test_virat_round_trip():
+    meta, ev, _ = S.read_adder(golden_bytes("virat_small_gray.adder"))
+    assert meta["time_mode"] == 1 and len(ev) == 96550
+    assert int(np.count_nonzero(ev["t"] % meta["ref_interval"] == 0)) == 1325
+    dt, bad = R.Migration(meta, R.DELTA_T).run(ev)
+    assert bad is None
+    back, bad = R.Migration(dict(meta, time_mode=0), R.ABSOLUTE_T).run(dt)
+    assert bad is None and times(back) == ev["t"].tolist()
+
+
+# ---- the fold ---------------------------------------------------------------------------------------------------
+
+def fold(events, **kw):
+    r = R.Info(meta_of(w=4, **kw))
+    assert r.run(events) is None
+    return r.min, r.max
+
+
+def test_fold_first_event_lowers_min_and_is_not_offered_to_max():
+    assert fold([ev1(3, 4)]) == (2.0, 0.0)
+    assert fold([ev1(3, 4), ev1(3, 2)]) == (2.0, 4.0)
+    # an event that lowers min would have raised max: it does not
+    assert fold([ev1(3, 4), ev1(3, 2), ev1(0, 1)]) == (1.0, 4.0)
+    assert fold([ev1(3, 4), ev1(0, 1), ev1(3, 2)]) == (1.0, 4.0)
+    assert fold([ev1(0, 1), ev1(3, 1), ev1(2, 1)]) == (1.0, 8.0)
+
+
+def test_fold_t_zero_is_dt_one():
+    assert fold([ev1(3, 0)]) == (8.0, 0.0)
+    assert fold([ev1(0, 4), ev1(127, 0)]) == (0.25, float(1 << 127))
+
+
+def test_fold_d_zero_integration_replaces_min_and_can_raise_it():
+    assert fold([ev1(0, 4), ev1(128, 2)]) == (0.5, 0.0)
+    assert fold([ev1(0, 4), ev1(128, 2), ev1(0, 3)]) == (1.0 / 3.0, 0.0)
+    assert fold([ev1(0, 4), ev1(128, 2), ev1(0, 1)]) == (0.5, 1.0)
+    assert fold([ev1(128, 0)]) == (math.inf, 0.0)  # 1.0 / 0
+    assert fold([ev1(128, 0), ev1(5, 1)]) == (32.0, 0.0)
+
+
+def test_fold_sticky_zero():
+    # d in 129..=254: intensity 0.0 < min, min = 0.0 for good; later events only reach max
+    assert fold([ev1(0, 4), ev1(200, 7), ev1(0, 8), ev1(128, 2), ev1(3, 1)]) == (0.0, 8.0)
+    assert fold([ev1(254, 1)]) == (0.0, 0.0)
+
+
+def test_fold_d_empty_is_ignored_but_advances_last_t_in_absolute_t():
+    assert fold([ev1(255, 1), ev1(0, 4)]) == (0.25, 0.0)
+    # AbsoluteT, v2: 100, then D_EMPTY at 300, then 400 -> dt 100 (not 300); no round-up to 255
+    assert fold([ev1(0, 100), ev1(255, 300), ev1(1, 400)], time_mode=1) == (0.01, 0.02)
+    assert fold([ev1(0, 100), ev1(1, 400)], time_mode=1) == (2.0 / 300.0, 0.0)
+    # v1 streams are never made relative, whatever the field says
+    assert fold([ev1(0, 100), ev1(1, 400)], time_mode=1, version=1) == (2.0 / 400.0, 0.0)
+    r = R.Info(meta_of(time_mode=1))
+    assert r.run([ev1(0, 100), ev1(0, 99)]) == 1 and r.count == 1
+
+
+def test_fold_units_are_separate_in_absolute_t():
+    assert fold([ev1(0, 100), ev1(0, 100, x=1), ev1(0, 300)], time_mode=1) == (0.005, 0.01)
+
+
+def test_drafted_figures_of_the_goldens():
+    def db(name):
+        meta, ev, _ = S.read_adder(golden_bytes(name))
+        r = R.Info(meta)
+        assert r.run(ev) is None
+        return r, meta, len(ev)
+    r, meta, n = db("adder_info_test_sample.adder")
+    assert n == 141 and (r.min, r.max) == (0.0090001406271973, 0.0382089552238806)
+    text = R.report(meta, 29, 1307, n, True, r.min, r.max)
+    assert "\t\t6.2792 dB (power)\n" in text
+    for name, want in (("bunny_v2_t.adder", "26.3858"), ("virat_small_gray.adder", "11.0957")):
+        r, meta, n = db(name)
+        assert f"\t\t{want} dB (power)\n" in R.report(meta, meta["header_size"], 0, n, True, r.min, r.max)
+    r, meta, n = db("sample_3_ordered.adder")
+    assert r.min == 0.0 and int(np.count_nonzero((S.read_adder(golden_bytes("sample_3_ordered.adder"))[1]["d"] > 128)
+                                                 & (S.read_adder(golden_bytes("sample_3_ordered.adder"))[1]["d"] < 255))) == 2
+    assert "\t\tinf dB (power)\n\t\tinf bits\n" in R.report(meta, meta["header_size"], 0, n, True, r.min, r.max)
+
+
+# ---- host helpers of the C-ABI ----------------------------------------------------------------------------------
+
+def lib_meta(meta):
+    return dict(width=meta["width"], height=meta["height"], channels=meta["channels"], codec_version=meta["version"],
+                time_mode=meta["time_mode"], ref_interval=meta["ref_interval"], source_camera=meta["source_camera"],
+                tps=meta["tps"], delta_t_max=meta["delta_t_max"])
+
+
+@pytest.mark.parametrize("name", GOLDENS)
+def test_header_parser_and_rewrite_on_every_golden(name):
+    from adder_amd import stream_tools as T
+    buf = golden_bytes(name)
+    want = S.parse_header(buf)
+    meta, hb, eb = T.parse_header(buf)
+    assert hb == want["header_size"] and eb == want["event_size"] and meta == lib_meta(want)
+    for mode in (0, 1, 2):
+        got = T.migrated_header(buf, mode)
+        assert got == R.migrated_header(buf, mode)
+        back = S.parse_header(got)
+        assert back["version"] == max(want["version"], 2) and back["time_mode"] == mode
+        for k in ("width", "height", "channels", "tps", "ref_interval", "delta_t_max", "source_camera", "event_size"):
+            assert back[k] == want[k], k
+
+
+def test_header_rewrite_of_nyc_is_the_golden_header_and_v3_keeps_its_tail():
+    from adder_amd import stream_tools as T
+    assert T.migrated_header(golden_bytes("nyc_v1_1px.adder"), 1) == golden_bytes("nyc_source_v2_2_1px.adder")[:33]
+    v3 = S.build_header(dict(meta_of(version=3, time_mode=0, cam=6), adu_interval=77))
+    got = T.migrated_header(v3, 1)
+    assert len(got) == 37 and got[:29] == v3[:29] and got[29:33] == b"\0\0\0\1" and got[33:] == v3[33:]
+    v0 = S.build_header(meta_of(version=0))
+    got = T.migrated_header(v0, 1)
+    assert got == v0[:5] + b"\2" + v0[6:25] + b"\0\0\0\0" + b"\0\0\0\1"  # FramedU8, AbsoluteT
+
+
+def test_header_helpers_refuse_what_is_not_a_raw_header():
+    from adder_amd import stream_tools as T, AdderHipError
+    buf = bytearray(golden_bytes("bunny_v2_dt.adder")[:64])
+    for bad in (b"", bytes(buf[:20]), b"xdder" + bytes(buf[5:]), bytes(buf[:5]) + b"\x09" + bytes(buf[6:]),
+                bytes(buf[:23]) + b"\x0a" + bytes(buf[24:])):
+        with pytest.raises(AdderHipError):
+            T.parse_header(bad)
+        with pytest.raises(AdderHipError):
+            T.migrated_header(bad, 1)
+    with pytest.raises(AdderHipError):
+        T.migrated_header(bytes(buf), 3)
+
+
+def test_report_holds_the_reference_strings_for_its_sample():
+    """adder-info's test_adder_info: ten strings as they stand, the two counts as we count them (141 / 35)"""
+    from adder_amd import stream_tools as T
+    buf = golden_bytes("adder_info_test_sample.adder")
+    meta, hb, _ = T.parse_header(buf)
+    _, ev, _ = S.read_adder(buf)
+    text = T.format_report(meta, hb, len(buf), len(ev), True, 0.0090001406271973, 0.0382089552238806)
+    for s in ("Width: 2", "Height: 2", "Color channels: 1", "Source camera: FramedU8", "Codec version: 1",
+              "Ticks per second: 120000", "ticks per source interval: 5000", "t_max: 240000", "File size: 1307",
+              "Header size: 29", "event count: 141", "Events per pixel channel: 35"):
+        assert s in text, s
+    assert text == R.report(S.parse_header(buf), hb, len(buf), len(ev), True, 0.0090001406271973, 0.0382089552238806)
+    assert text.endswith("Dynamic range\n\tTheoretical range:\n\t\t-inf dB (power)\n\t\t-inf bits\n\tRealized range:\n"
+                         "\t\t6.2792 dB (power)\n\t\t2.0859 bits\n")
+    short = T.format_report(meta, hb, len(buf), len(ev))
+    assert text.startswith(short) and short.endswith("Events per pixel channel: 35\n")
+    assert "\tTime mode: AbsoluteT\n" in text  # a v1 header: the reference's decoder keeps its default
+
+
+@pytest.mark.parametrize("lo,hi", [(0.0, 1.0), (0.0, 0.0), (math.inf, 0.0), (math.inf, 1.0), (R.F64_MAX, 0.0),
+                                   (0.5, 0.25), (1.0, 1.0), (3.0, 1e300), (0.1, 0.30000000000000004),
+                                   (1.0, 10.0 ** 0.000125), (1.0, 10.0 ** 0.000375)])
+def test_report_numbers_are_rust_formatted(lo, hi):
+    from adder_amd import stream_tools as T
+    for meta in (meta_of(w=3, h=2, ch=3, version=2, time_mode=0, cam=6), meta_of(version=3, time_mode=2, cam=9, dtm=0)):
+        got = T.format_report(lib_meta(meta), 33, 12345, 999, True, lo, hi)
+        assert got == R.report(meta, 33, 12345, 999, True, lo, hi)
+    tail = got.split("Realized range:\n")[1]
+    if lo == 0.0 and hi > 0:
+        assert tail == "\t\tinf dB (power)\n\t\tinf bits\n"
+    if lo == 0.0 and hi == 0.0:
+        assert tail == "\t\tNaN dB (power)\n\t\tNaN bits\n"
+    if math.isinf(lo) and hi == 0.0:
+        assert tail == "\t\t-inf dB (power)\n\t\t-inf bits\n"
+    if (lo, hi) == (0.5, 0.25):
+        assert tail == "\t\t-3.0103 dB (power)\n\t\t-1.0000 bits\n"
+
+
+def test_stream_symbols_equal_their_binding_table():
+    import ctypes
+    import adder_amd
+    from adder_amd import stream_tools as T
+    hdr = open(os.path.join(ROOT, "include", "adder_stream.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    names = set(re.findall(r"\b(adder_stream_\w+)\s*\(", hdr))
+    assert len(names) >= 16 and names == set(T.SYMBOLS)
+    adder_amd.load()
+    L = ctypes.CDLL(adder_amd.LIB_PATH)
+    for n in names:
+        assert hasattr(L, n), n
+
+
+def test_params_struct_layout():
+    import ctypes
+    from adder_amd import stream_tools as T
+    assert ctypes.sizeof(T.AdderStreamParams) == 32 and T.AdderStreamParams.ref_interval.offset == 12
+
+
+def test_no_cpu_fallback_without_a_device():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    from adder_amd import stream_tools as T, AdderHipError
+    for make in (lambda: T.HipStreamMigrator(8, 8), lambda: T.HipStreamInfo(8, 8)):
+        with pytest.raises(AdderHipError) as ei:
+            make()
+        assert ei.value.code == -3
+
+
+def test_create_refuses_bad_parameters():
+    import ctypes as C
+    from adder_amd import stream_tools as T
+    L = T.load()
+    h = C.c_void_p()
+    for kw in (dict(abi_version=2), dict(width=0), dict(channels=2), dict(ref_interval=0), dict(codec_version=4),
+               dict(out_time_mode=3)):
+        base = dict(abi_version=1, width=4, height=4, channels=1, codec_version=2, ref_interval=255)
+        p = T.AdderStreamParams(**dict(base, **kw))
+        assert L.adder_stream_create(C.byref(p), C.byref(h)) == -1 and not h.value
+        assert L.adder_stream_last_error(None)
+
+
+def build_example(tmp_path):
+    import adder_amd
+    adder_amd.load()
+    lib = os.path.join(ROOT, "adder-codec-rs_amd")
+    exe = str(tmp_path / "adder_migrate")
+    subprocess.check_call(["gcc", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "adder_migrate.c"), "-L", lib, "-ladder_hip",
+                           "-Wl,-rpath," + lib, "-o", exe])
+    return exe
+
+
+def test_migrate_example_compiles_with_warnings_as_errors(tmp_path):
+    assert os.path.exists(build_example(tmp_path))
