@@ -32,6 +32,8 @@ EVENT_DTYPE = np.dtype(
     [("x", "<u2"), ("y", "<u2"), ("c", "u1"), ("d", "u1"), ("pad", "<u2"), ("t", "<u4")]
 )
 assert EVENT_DTYPE.itemsize == 12
+FRAMER_FEATURE_DTYPE = np.dtype([("index", "<u8"), ("t", "<u4"), ("x", "<u2"), ("y", "<u2")])  # AdderFramerFeature
+assert FRAMER_FEATURE_DTYPE.itemsize == 16
 
 
 class AdderHipParams(C.Structure):
@@ -235,6 +237,14 @@ SYMBOLS = {
     "adder_framer_pop": (_i32, [_vp, _vp, _u32, C.POINTER(_u32)]),
     "adder_framer_write_frame": (_i32, [_vp, _vp]),
     "adder_framer_flush": (_i32, [_vp, C.POINTER(_i32)]),
+    "adder_framer_detect_features": (_i32, [_vp, _i32]),
+    "adder_framer_reset_last_event": (_i32, [_vp]),
+    "adder_framer_reserve_features": (_i32, [_vp, _u64]),
+    "adder_framer_features": (_i32, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    "adder_framer_features_device": (_i32, [_vp, _vp, _u64, C.POINTER(_u64), _vp]),
+    "adder_framer_pop_features": (_i32, [_vp, C.POINTER(_u64), _vp, _u32, C.POINTER(_u32)]),
+    "adder_framer_running_intensities": (_i32, [_vp, _vp]),
+    "adder_framer_running_intensities_device": (_i32, [_vp, _vp, _vp]),
 }
 
 _lib = None

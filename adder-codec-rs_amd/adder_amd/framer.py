@@ -118,6 +118,62 @@ class HipFramer:
         N.check_framer(self.h, self.L.adder_framer_flush(self.h, C.byref(r)))
         return bool(r.value)
 
+    # ---- feature detection while framing (FrameSequence::detect_features, driver.rs:482-553) ----
+
+    def detect_features(self, on):
+        """Framer::detect_features: FAST 9_16 on the running intensities as each event arrives; all ingest_* detect."""
+        N.check_framer(self.h, self.L.adder_framer_detect_features(self.h, 1 if on else 0))
+
+    def reserve_features(self, max_events):
+        """Allocates now what detection needs for calls of up to max_events events (else the first such call does)."""
+        N.check_framer(self.h, self.L.adder_framer_reserve_features(self.h, max_events))
+
+    def reset_last_event(self):
+        """The player's `last_event = None` (otherwise the last event's t is carried from call to call)."""
+        N.check_framer(self.h, self.L.adder_framer_reset_last_event(self.h))
+
+    def features(self):
+        """The features of the last ingest call, stream order: array of FRAMER_FEATURE_DTYPE {index, t, x, y}."""
+        n = C.c_uint64(0)
+        rc = self.L.adder_framer_features(self.h, None, 0, C.byref(n))
+        if rc == N.OK:
+            return np.zeros(0, N.FRAMER_FEATURE_DTYPE)
+        if rc != N.E_OUT_CAPACITY:
+            N.check_framer(self.h, rc)
+        out = np.zeros(n.value, N.FRAMER_FEATURE_DTYPE)
+        N.check_framer(self.h, self.L.adder_framer_features(self.h, out.ctypes.data, len(out), C.byref(n)))
+        return out[: n.value]
+
+    def features_device(self, d_out, stream=None):
+        """The same into a CUDA tensor of 16-byte records; returns their number."""
+        n = C.c_uint64(0)
+        N.check_framer(self.h, self.L.adder_framer_features_device(
+            self.h, d_out.data_ptr(), d_out.numel() * d_out.element_size() // 16, C.byref(n),
+            C.c_void_p(stream) if stream else None))
+        return n.value
+
+    def pop_features(self):
+        """FrameSequence::pop_features: (end_ts, [n][2] u16 array of (x, y))."""
+        end_ts, n = C.c_uint64(0), C.c_uint32(0)
+        rc = self.L.adder_framer_pop_features(self.h, C.byref(end_ts), None, 0, C.byref(n))
+        if rc == N.OK:
+            return end_ts.value, np.zeros((0, 2), np.uint16)
+        if rc != N.E_OUT_CAPACITY:
+            N.check_framer(self.h, rc)
+        xy = np.zeros((n.value, 2), np.uint16)
+        N.check_framer(self.h, self.L.adder_framer_pop_features(self.h, C.byref(end_ts), xy.ctypes.data, len(xy), C.byref(n)))
+        return end_ts.value, xy
+
+    def running_intensities(self):
+        """FrameSequence::get_running_intensities: [height][width][channels] u8."""
+        out = np.zeros((self.height, self.width, self.channels), np.uint8)
+        N.check_framer(self.h, self.L.adder_framer_running_intensities(self.h, out.ctypes.data))
+        return out
+
+    def running_intensities_device(self, d_out, stream=None):
+        N.check_framer(self.h, self.L.adder_framer_running_intensities_device(
+            self.h, d_out.data_ptr(), C.c_void_p(stream) if stream else None))
+
 
 def contiguous_run_segments(events):
     """Greedy split of an arbitrary event stream into segments inside which every pixel-channel's

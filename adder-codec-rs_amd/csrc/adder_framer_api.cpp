@@ -7,11 +7,14 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <new>
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 #include "../../include/adder_framer.h"
+#include "adder_framer_features.h"
 #include "adder_framer_kernels.h"
 
 using namespace adder;
@@ -51,6 +54,27 @@ struct AdderFramer {
     bool flushed_pending = false;
     bool poisoned = false;
     std::string err;
+    // feature detection while framing (adder_framer_detect_features); allocated when it is first switched on
+    struct FeatureInterval {  // driver.rs:252-257
+        uint64_t end_ts;
+        std::vector<uint16_t> xy;
+    };
+    bool detect = false;
+    uint8_t *plane = nullptr;            // running_intensities [h][w][c]
+    uint32_t *carry = nullptr;           // device {valid, t} of the last event ingested with detection on
+    uint32_t *feat_count = nullptr;      // device
+    uint2 *feat_runs = nullptr;          // [n_units]
+    uint8_t *feat_scratch = nullptr;     // per-call arrays (FramerFeatureScratch)
+    size_t feat_scratch_cap = 0;
+    AdderFramerFeature *feat_out = nullptr;  // the last call's features on the device
+    size_t feat_out_cap = 0;
+    bool feat_pending = false;           // ... not yet read back and filed in `intervals`
+    int64_t feat_fw = 0;                 // frames_written during that call
+    uint64_t feat_index_bias = 0;        // adder_framer_ingest: its device copy starts at the first segment
+    std::vector<AdderFramerFeature> feat_host;
+    std::deque<FeatureInterval> intervals;   // FrameSequence::features
+    bool intervals_broken = false;       // the reference would have panicked
+    std::string intervals_err;
 };
 
 static int ffail(AdderFramer *fr, int code, const char *fmt, ...) {
@@ -79,7 +103,9 @@ static void framer_free(AdderFramer *fr) {
     (void)hipSetDevice(fr->device);
     if (fr->stream) (void)hipStreamSynchronize(fr->stream);
     for (void *p : {(void *)fr->px, (void *)fr->ring, (void *)fr->status,
-                    (void *)fr->minmax, (void *)fr->d_events, (void *)fr->d_out, (void *)fr->d_offs, (void *)fr->d_tile_off})
+                    (void *)fr->minmax, (void *)fr->d_events, (void *)fr->d_out, (void *)fr->d_offs, (void *)fr->d_tile_off,
+                    (void *)fr->plane, (void *)fr->carry, (void *)fr->feat_count, (void *)fr->feat_runs,
+                    (void *)fr->feat_scratch, (void *)fr->feat_out})
         if (p) (void)hipFree(p);
     if (fr->h_offs) (void)hipHostFree(fr->h_offs);
     if (fr->h_offs_big) (void)hipHostFree(fr->h_offs_big);
@@ -258,6 +284,10 @@ static int check_status(AdderFramer *fr) {
                  fr->ring_frames);
 }
 
+static int ingest_with_features(AdderFramer *fr, const AdderEvent *d_events, const uint64_t *seg_offsets,
+                                uint32_t num_segments, const FramerArgs &a, hipStream_t s);
+static int settle_features(AdderFramer *fr);
+
 extern "C" int adder_framer_ingest_device(AdderFramer *fr, const AdderEvent *d_events, const uint64_t *seg_offsets,
                                           uint32_t num_segments, void *stream) {
     if (!fr) return ADDER_E_BAD_PARAMS;
@@ -271,6 +301,7 @@ extern "C" int adder_framer_ingest_device(AdderFramer *fr, const AdderEvent *d_e
         if (rc_ != ADDER_OK) return rc_;
     }
     const FramerArgs a = make_args(fr);
+    if (fr->detect) return ingest_with_features(fr, d_events, seg_offsets, num_segments, a, (hipStream_t)stream);
     for (uint32_t s = 0; s < num_segments; ++s) {
         if (seg_offsets[s + 1] < seg_offsets[s]) return ffail(fr, ADDER_E_BAD_PARAMS, "segment offsets must not decrease");
         FHIPCHK(fr, adder_framer_launch_segment(d_events, seg_offsets[s], seg_offsets[s + 1], &a, (hipStream_t)stream));
@@ -291,8 +322,8 @@ extern "C" int adder_framer_ingest_frames_device(AdderFramer *fr, const AdderEve
         return ffail(fr, ADDER_E_BAD_PARAMS, "null argument");
     for (uint32_t s = 0; s < num_frames; ++s)
         if (frame_offsets[s + 1] < frame_offsets[s]) return ffail(fr, ADDER_E_BAD_PARAMS, "frame offsets must not decrease");
-    // u16 / u32 frames: the per-event kernel (the tile kernel's LDS window holds bytes)
-    if (fr->p.value_type != ADDER_FRAME_U8) return adder_framer_ingest_device(fr, d_events, frame_offsets, num_frames, stream);
+    // u16 / u32 frames: the per-event kernel (the tile kernel's LDS window holds bytes); so does detection
+    if (fr->p.value_type != ADDER_FRAME_U8 || fr->detect) return adder_framer_ingest_device(fr, d_events, frame_offsets, num_frames, stream);
     FHIPCHK(fr, hipSetDevice(fr->device));
     hipStream_t s = (hipStream_t)stream;
     {
@@ -337,6 +368,15 @@ extern "C" int adder_framer_ingest_frames_device_offsets(AdderFramer *fr, const 
     if (fr->flushed_pending) return ffail(fr, ADDER_E_BAD_PARAMS, "pop the flushed frame before ingesting more events");
     if (!num_frames) return ADDER_OK;
     if (!d_frame_offsets || !d_events) return ffail(fr, ADDER_E_BAD_PARAMS, "null argument");
+    if (fr->detect) {  // the general path takes the ends of the range from the host: read them back
+        FHIPCHK(fr, hipSetDevice(fr->device));
+        uint64_t ends[2];
+        FHIPCHK(fr, hipMemcpyAsync(&ends[0], d_frame_offsets, sizeof(uint64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        FHIPCHK(fr, hipMemcpyAsync(&ends[1], d_frame_offsets + num_frames, sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                   (hipStream_t)stream));
+        FHIPCHK(fr, hipStreamSynchronize((hipStream_t)stream));
+        return adder_framer_ingest_device(fr, d_events, ends, 1u, stream);
+    }
     if (fr->p.value_type != ADDER_FRAME_U8)
         return ffail(fr, ADDER_E_BAD_PARAMS, "u16 / u32 frames take their segment offsets from host memory "
                      "(adder_framer_ingest_frames_device / adder_framer_ingest_device)");
@@ -381,7 +421,9 @@ extern "C" int adder_framer_ingest(AdderFramer *fr, const AdderEvent *events, co
     uint64_t *offs = num_segments + 1 <= 64 ? small : new (std::nothrow) uint64_t[num_segments + 1];
     if (!offs) return ffail(fr, ADDER_E_HIP, "out of host memory");
     for (uint32_t s = 0; s <= num_segments; ++s) offs[s] = seg_offsets[s] - e0;
+    fr->feat_index_bias = e0;
     rc = adder_framer_ingest_device(fr, fr->d_events, offs, num_segments, fr->stream);
+    fr->feat_index_bias = 0;
     if (offs != small) delete[] offs;
     if (rc != ADDER_OK) return rc;
     return check_status(fr);
@@ -432,6 +474,10 @@ extern "C" int adder_framer_pop_device(AdderFramer *fr, uint8_t *d_out, uint32_t
     if (fr->poisoned) return ffail(fr, ADDER_E_POISONED, "context is poisoned by an earlier failure: %s", fr->err.c_str());
     if (!d_out && max_frames) return ffail(fr, ADDER_E_BAD_PARAMS, "null output");
     FHIPCHK(fr, hipSetDevice(fr->device));
+    if (fr->feat_pending) {  // the features of the last call are filed under the frames_written it ran with
+        const int rc_ = settle_features(fr);
+        if (rc_ != ADDER_OK) return rc_;
+    }
     hipStream_t s = (hipStream_t)stream;
     uint32_t ready = 0;
     const int rc = ready_count(fr, &ready, s);
@@ -481,6 +527,10 @@ extern "C" int adder_framer_write_frame(AdderFramer *fr, uint8_t *out) {
     if (rc != ADDER_OK) return rc;
     rc = fensure(fr, &fr->d_out, &fr->d_out_cap, (size_t)fr->n_units << fr->p.value_type);
     if (rc != ADDER_OK) return rc;
+    if (fr->feat_pending) {
+        rc = settle_features(fr);
+        if (rc != ADDER_OK) return rc;
+    }
     // frame 0 as it is: pixels that have no value yet read 0 (driver.rs:946-950); after a flush
     // every pixel has one
     FHIPCHK(fr, adder_framer_launch_pop(fr->ring, fr->px, fr->n_units, fr->ring_frames, (int32_t)fr->frames_written, 1u,
@@ -515,4 +565,252 @@ extern "C" int adder_framer_flush(AdderFramer *fr, int *frame0_ready) {
         if (frame0_ready) *frame0_ready = 1;
     }
     return ADDER_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Feature detection while framing (include/adder_framer.h; kernels in adder_framer_features.hip)
+// ---------------------------------------------------------------------------------------------------------------
+
+// driver.rs:497-549 for one feature found at `time`, with the frames_written the context had during the call
+static void file_feature(AdderFramer *fr, uint32_t time, uint16_t x, uint16_t y, int64_t frames_written) {
+    if (fr->intervals_broken) return;
+    auto &dq = fr->intervals;
+    const uint32_t tpf = fr->tpf;
+    size_t idx = (int64_t)(time / tpf) >= frames_written ? (size_t)(uint32_t)(time / tpf - (uint32_t)frames_written) : 0u;
+    if (time % tpf == 0u && idx > 0u) idx -= 1u;
+    auto broken = [&](const char *why) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "the feature at t = %u (%u, %u) %s (frames_written %lld, %zu intervals): it and every "
+                 "later feature is not filed", time, x, y, why, (long long)frames_written, dq.size());
+        fr->intervals_broken = true;
+        fr->intervals_err = buf;
+    };
+    if (idx >= dq.size()) {
+        if (dq.empty()) {
+            dq.push_back({(uint64_t)tpf, {}});
+            dq.push_back({(uint64_t)tpf * 2u, {}});
+        }
+        const uint64_t new_end_ts = time % tpf == 0u ? time : (uint32_t)((time / tpf + 1u) * tpf);  // u32, wrapping
+        uint64_t running_end_ts = dq.back().end_ts + tpf;
+        if (running_end_ts <= new_end_ts && (new_end_ts - running_end_ts) / tpf >= (1u << 22))
+            return broken("would grow the interval deque by more than 2^22 intervals");
+        while (running_end_ts <= new_end_ts) {
+            dq.push_back({running_end_ts, {}});
+            running_end_ts += tpf;
+        }
+    }
+    if (idx >= dq.size()) return broken("lies past the interval deque, where the reference panics");
+    if (dq[idx].end_ts < (uint64_t)time) dq[idx].end_ts = time;  // detection switched on late (:544-547)
+    dq[idx].xy.push_back(x);
+    dq[idx].xy.push_back(y);
+}
+
+// reads the last call's features back and files them; waits for that call
+static int settle_features(AdderFramer *fr) {
+    if (!fr->feat_pending) return ADDER_OK;
+    {
+        const int rc_ = after_last_op(fr, fr->stream);
+        if (rc_ != ADDER_OK) return rc_;
+    }
+    uint32_t n = 0;
+    FHIPCHK(fr, hipMemcpyAsync(&n, fr->feat_count, sizeof n, hipMemcpyDeviceToHost, fr->stream));
+    FHIPCHK(fr, hipStreamSynchronize(fr->stream));
+    fr->feat_host.resize(n);
+    if (n) {
+        FHIPCHK(fr, hipMemcpyAsync(fr->feat_host.data(), fr->feat_out, (size_t)n * sizeof(AdderFramerFeature),
+                                   hipMemcpyDeviceToHost, fr->stream));
+        FHIPCHK(fr, hipStreamSynchronize(fr->stream));
+    }
+    fr->feat_pending = false;
+    for (const AdderFramerFeature &f : fr->feat_host) file_feature(fr, f.t, f.x, f.y, fr->feat_fw);
+    return ADDER_OK;
+}
+
+static size_t feat_align(size_t v) { return (v + 255u) & ~(size_t)255u; }
+
+// the per-call arrays of a call of n events, carved from one allocation that only grows; and room for its features
+static int features_scratch(AdderFramer *fr, uint64_t n, FramerFeatureScratch *out) {
+    FramerFeatureScratch sc{};
+    sc.temp_bytes = framer_features_temp_bytes(n);
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = off;
+        off += feat_align(bytes);
+        return at;
+    };
+    const size_t o_k0 = carve(4u * n), o_k1 = carve(4u * n), o_i0 = carve(4u * n), o_i1 = carve(4u * n), o_vs = carve(n),
+                 o_vi = carve(n), o_ta = carve(4u * n), o_mk = carve(n), o_of = carve(4u * n), o_tmp = carve(sc.temp_bytes);
+    int rc = fensure(fr, &fr->feat_scratch, &fr->feat_scratch_cap, off);
+    if (rc != ADDER_OK) return rc;
+    rc = fensure(fr, &fr->feat_out, &fr->feat_out_cap, (size_t)n * sizeof(AdderFramerFeature));
+    if (rc != ADDER_OK) return rc;
+    uint8_t *b = fr->feat_scratch;
+    sc.keys0 = reinterpret_cast<uint32_t *>(b + o_k0);
+    sc.keys1 = reinterpret_cast<uint32_t *>(b + o_k1);
+    sc.idx0 = reinterpret_cast<uint32_t *>(b + o_i0);
+    sc.idx1 = reinterpret_cast<uint32_t *>(b + o_i1);
+    sc.val8_sorted = b + o_vs;
+    sc.val8_input = b + o_vi;
+    sc.t_after = reinterpret_cast<uint32_t *>(b + o_ta);
+    sc.mark = b + o_mk;
+    sc.offs = reinterpret_cast<uint32_t *>(b + o_of);
+    sc.temp = b + o_tmp;
+    *out = sc;
+    return ADDER_OK;
+}
+
+static int ingest_with_features(AdderFramer *fr, const AdderEvent *d_events, const uint64_t *seg_offsets,
+                                uint32_t num_segments, const FramerArgs &a, hipStream_t s) {
+    for (uint32_t k = 0; k < num_segments; ++k)
+        if (seg_offsets[k + 1] < seg_offsets[k]) return ffail(fr, ADDER_E_BAD_PARAMS, "segment offsets must not decrease");
+    const uint64_t e0 = num_segments ? seg_offsets[0] : 0u, e1 = num_segments ? seg_offsets[num_segments] : 0u;
+    const uint64_t n = e1 - e0;
+    if (n >= (1ull << 31))
+        return ffail(fr, ADDER_E_BAD_PARAMS, "a call with feature detection on takes fewer than 2^31 events");
+    int rc = settle_features(fr);  // the previous call's features leave the device buffers first
+    if (rc != ADDER_OK) return rc;
+    fr->feat_host.clear();
+    if (n == 0u) return mark_op(fr, s);  // an empty call: no features, plane and carried event as they were
+    FramerFeatureScratch sc{};
+    rc = features_scratch(fr, n, &sc);
+    if (rc != ADDER_OK) return rc;
+    sc.runs = fr->feat_runs;
+    FramerFeatureState st{};
+    st.plane = fr->plane;
+    st.carry = fr->carry;
+    st.out = fr->feat_out;
+    st.out_cap = n;
+    st.count = fr->feat_count;
+    uint32_t key_bits = 0;
+    while (((uint64_t)1 << key_bits) < (uint64_t)fr->n_units + 1u) ++key_bits;
+    FHIPCHK(fr, framer_features_run(reinterpret_cast<const uint32_t *>(d_events + e0), n, e0 + fr->feat_index_bias, a,
+                                    key_bits, sc, st, s));
+    fr->feat_pending = true;
+    fr->feat_fw = fr->frames_written;
+    return mark_op(fr, s);
+}
+
+extern "C" int adder_framer_detect_features(AdderFramer *fr, int on) {
+    if (!fr) return ADDER_E_BAD_PARAMS;
+    if (fr->poisoned) return ffail(fr, ADDER_E_POISONED, "context is poisoned by an earlier failure: %s", fr->err.c_str());
+    if (on && (fr->p.row_begin != 0u || fr->p.row_end != fr->p.height))
+        return ffail(fr, ADDER_E_BAD_PARAMS, "feature detection needs the whole plane: this context owns rows [%u, %u) and "
+                     "the FAST ring reaches 3 rows over", fr->p.row_begin, fr->p.row_end);
+    if (on && !fr->plane) {
+        FHIPCHK(fr, hipSetDevice(fr->device));
+        FHIPCHK(fr, hipMalloc(reinterpret_cast<void **>(&fr->plane), fr->n_units));
+        FHIPCHK(fr, hipMalloc(reinterpret_cast<void **>(&fr->carry), 2 * sizeof(uint32_t)));
+        FHIPCHK(fr, hipMalloc(reinterpret_cast<void **>(&fr->feat_count), sizeof(uint32_t)));
+        FHIPCHK(fr, hipMalloc(reinterpret_cast<void **>(&fr->feat_runs), (size_t)fr->n_units * sizeof(uint2)));
+        FHIPCHK(fr, hipMemsetAsync(fr->plane, 0, fr->n_units, fr->stream));
+        FHIPCHK(fr, hipMemsetAsync(fr->carry, 0, 2 * sizeof(uint32_t), fr->stream));
+        FHIPCHK(fr, hipMemsetAsync(fr->feat_count, 0, sizeof(uint32_t), fr->stream));
+        FHIPCHK(fr, hipStreamSynchronize(fr->stream));
+    }
+    fr->detect = on != 0;
+    return ADDER_OK;
+}
+
+extern "C" int adder_framer_reserve_features(AdderFramer *fr, uint64_t max_events) {
+    if (!fr) return ADDER_E_BAD_PARAMS;
+    if (max_events >= (1ull << 31))
+        return ffail(fr, ADDER_E_BAD_PARAMS, "a call with feature detection on takes fewer than 2^31 events");
+    FHIPCHK(fr, hipSetDevice(fr->device));
+    const int rc = settle_features(fr);  // growing frees the buffers the last call's features sit in
+    if (rc != ADDER_OK) return rc;
+    FramerFeatureScratch sc{};
+    return max_events ? features_scratch(fr, max_events, &sc) : ADDER_OK;
+}
+
+extern "C" int adder_framer_reset_last_event(AdderFramer *fr) {
+    if (!fr) return ADDER_E_BAD_PARAMS;
+    if (!fr->carry) return ADDER_OK;  // nothing was ever carried
+    FHIPCHK(fr, hipSetDevice(fr->device));
+    const int rc = after_last_op(fr, fr->stream);
+    if (rc != ADDER_OK) return rc;
+    FHIPCHK(fr, hipMemsetAsync(fr->carry, 0, 2 * sizeof(uint32_t), fr->stream));
+    return mark_op(fr, fr->stream);
+}
+
+extern "C" int adder_framer_features(AdderFramer *fr, AdderFramerFeature *out, uint64_t capacity, uint64_t *count) {
+    if (!fr || !count) return ADDER_E_BAD_PARAMS;
+    FHIPCHK(fr, hipSetDevice(fr->device));
+    const int rc = settle_features(fr);
+    if (rc != ADDER_OK) return rc;
+    *count = fr->feat_host.size();
+    if (*count > capacity || (*count && !out))
+        return ffail(fr, ADDER_E_OUT_CAPACITY, "%llu features, room for %llu", (unsigned long long)*count,
+                     (unsigned long long)capacity);
+    if (*count) memcpy(out, fr->feat_host.data(), (size_t)*count * sizeof(AdderFramerFeature));
+    return ADDER_OK;
+}
+
+extern "C" int adder_framer_features_device(AdderFramer *fr, AdderFramerFeature *d_out, uint64_t capacity,
+                                            uint64_t *count, void *stream) {
+    if (!fr || !count) return ADDER_E_BAD_PARAMS;
+    FHIPCHK(fr, hipSetDevice(fr->device));
+    int rc = settle_features(fr);
+    if (rc != ADDER_OK) return rc;
+    *count = fr->feat_host.size();
+    if (*count > capacity || (*count && !d_out))
+        return ffail(fr, ADDER_E_OUT_CAPACITY, "%llu features, room for %llu", (unsigned long long)*count,
+                     (unsigned long long)capacity);
+    if (!*count) return ADDER_OK;
+    rc = after_last_op(fr, (hipStream_t)stream);
+    if (rc != ADDER_OK) return rc;
+    FHIPCHK(fr, hipMemcpyAsync(d_out, fr->feat_out, (size_t)*count * sizeof(AdderFramerFeature), hipMemcpyDeviceToDevice,
+                               (hipStream_t)stream));
+    return mark_op(fr, (hipStream_t)stream);  // the next call overwrites the buffer this copy reads
+}
+
+extern "C" int adder_framer_pop_features(AdderFramer *fr, uint64_t *end_ts, uint16_t *xy, uint32_t capacity,
+                                         uint32_t *count) {
+    if (!fr || !end_ts || !count) return ADDER_E_BAD_PARAMS;
+    FHIPCHK(fr, hipSetDevice(fr->device));
+    const int rc = settle_features(fr);
+    if (rc != ADDER_OK) return rc;
+    if (fr->intervals_broken) return ffail(fr, ADDER_E_BAD_PARAMS, "%s", fr->intervals_err.c_str());
+    auto &dq = fr->intervals;
+    const size_t n = dq.empty() ? 0u : dq.front().xy.size() / 2u;
+    *count = (uint32_t)n;
+    if (n > capacity || (n && !xy))
+        return ffail(fr, ADDER_E_OUT_CAPACITY, "%zu features in the interval, room for %u", n, capacity);
+    // driver.rs:851-873
+    if (dq.empty()) {
+        dq.push_back({(uint64_t)fr->tpf, {}});
+        dq.push_back({(uint64_t)fr->tpf * 2u, {}});
+    } else {
+        dq.push_back({(uint64_t)fr->tpf + dq.back().end_ts, {}});
+    }
+    *end_ts = dq.front().end_ts;
+    if (n) memcpy(xy, dq.front().xy.data(), n * 2u * sizeof(uint16_t));
+    dq.pop_front();
+    return ADDER_OK;
+}
+
+extern "C" int adder_framer_running_intensities(AdderFramer *fr, uint8_t *out) {
+    if (!fr || !out) return ADDER_E_BAD_PARAMS;
+    if (!fr->plane) {  // detection was never on
+        memset(out, 0, fr->n_units);
+        return ADDER_OK;
+    }
+    FHIPCHK(fr, hipSetDevice(fr->device));
+    const int rc = after_last_op(fr, fr->stream);
+    if (rc != ADDER_OK) return rc;
+    FHIPCHK(fr, hipMemcpyAsync(out, fr->plane, fr->n_units, hipMemcpyDeviceToHost, fr->stream));
+    FHIPCHK(fr, hipStreamSynchronize(fr->stream));
+    return ADDER_OK;
+}
+
+extern "C" int adder_framer_running_intensities_device(AdderFramer *fr, uint8_t *d_out, void *stream) {
+    if (!fr || !d_out) return ADDER_E_BAD_PARAMS;
+    FHIPCHK(fr, hipSetDevice(fr->device));
+    if (!fr->plane) {
+        FHIPCHK(fr, hipMemsetAsync(d_out, 0, fr->n_units, (hipStream_t)stream));
+        return ADDER_OK;
+    }
+    const int rc = after_last_op(fr, (hipStream_t)stream);
+    if (rc != ADDER_OK) return rc;
+    FHIPCHK(fr, hipMemcpyAsync(d_out, fr->plane, fr->n_units, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return mark_op(fr, (hipStream_t)stream);
 }

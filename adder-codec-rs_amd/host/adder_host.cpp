@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "../../include/adder_compressed.h"
+#include "../csrc/adder_framer.hpp"  // framer_value: get_frame_value for the host's FeatureTracker
 
 #include <chrono>
 
@@ -934,6 +935,9 @@ FrameSequence::FrameSequence(const FramerBuilder &b, FrameElement element) : chu
     width_ = b.plane_.w();
     height_ = b.plane_.h();
     channels_ = b.plane_.c();
+    tracker_ = std::make_unique<FeatureTracker>(b.plane_, adder_framer_tpf(fr_), p.ref_interval, p.delta_t_max, p.codec_version,
+                                                b.time_mode_, b.source_camera_, p.view_mode, p.source_type, p.practical_d_max,
+                                                p.value_type);
 }
 
 FrameSequence::~FrameSequence() { adder_framer_destroy(fr_); }
@@ -953,6 +957,17 @@ bool FrameSequence::is_frame_0_filled() {
 bool FrameSequence::ingest_event(Event &event) {
     const uint64_t offs[2] = {0, 1};
     framer_check(fr_, adder_framer_ingest(fr_, &event, offs, 1));
+    if (armed_) {
+        Event seen = event;  // (this overload leaves the caller's event as it is)
+        tracker_->ingest_event(seen, std::nullopt, frames_written());
+    }
+    return is_frame_0_filled();
+}
+
+bool FrameSequence::ingest_event(Event &event, const std::optional<Event> &last_event) {
+    const uint64_t offs[2] = {0, 1};
+    framer_check(fr_, adder_framer_ingest(fr_, &event, offs, 1));
+    if (armed_) tracker_->ingest_event(event, last_event, frames_written());
     return is_frame_0_filled();
 }
 
@@ -981,6 +996,12 @@ bool FrameSequence::ingest_events_events(const std::vector<std::vector<Event>> &
     }
     seg_offs_.push_back(flat_.size());
     framer_check(fr_, adder_framer_ingest(fr_, flat_.data(), seg_offs_.data(), (uint32_t)seg_offs_.size() - 1));
+    if (armed_) {  // the bulk path never detects (:564-626); the host trackers follow it
+        const bool on = tracker_->detect_features;
+        tracker_->detect_features = false;
+        for (Event e : flat_) tracker_->ingest_event(e, std::nullopt, 0);
+        tracker_->detect_features = on;
+    }
     return is_frame_0_filled();
 }
 
@@ -1008,6 +1029,134 @@ int FrameSequence::write_multi_frame_bytes(std::ostream &writer) {
         if (n < 64) break;
     }
     return frames;
+}
+
+// ---------------------------------------------------------------- FeatureTracker (driver.rs:482-553, utils/cv.rs)
+FeatureTracker::FeatureTracker(PlaneSize plane, uint32_t tpf, uint32_t ref_interval, uint32_t delta_t_max,
+                               uint8_t codec_version, TimeMode time_mode, SourceCamera camera, uint8_t view_mode,
+                               uint8_t source_type, float practical_d_max, uint8_t element)
+    : w_(plane.w()), h_(plane.h()), c_(plane.c()), tpf_(tpf), ref_interval_(ref_interval), delta_t_max_(delta_t_max),
+      abs_t_(codec_version >= 2 && time_mode == TimeMode::AbsoluteT),
+      round_up_(codec_version >= 1 && (uint32_t)camera <= (uint32_t)SourceCamera::FramedF64), view_mode_(view_mode),
+      source_type_(source_type), element_(element), practical_d_max_(practical_d_max) {
+    const size_t n = (size_t)w_ * h_ * c_;
+    ts_.assign(n, 0);
+    lastf_.assign(n, -1);
+    lasti_.assign(n, 0);
+    running_.assign(n, 0);
+}
+
+// is_feature (cv.rs:56-212): border and channel, the opposite-pair rejects, then a streak of 9 around the circle
+bool FeatureTracker::is_feature(const Event &e) const {
+    static const int kCircle[16][2] = {{0, 3}, {1, 3}, {2, 2}, {3, 1}, {3, 0}, {3, -1}, {2, -2}, {1, -3},
+                                       {0, -3}, {-1, -3}, {-2, -2}, {-3, -1}, {-3, 0}, {-3, 1}, {-2, 2}, {-1, 3}};
+    if (e.x < 3 || e.y < 3 || (uint32_t)e.x + 3 >= w_ || (uint32_t)e.y + 3 >= h_) return false;
+    if (!(e.c == 0 || e.c == ADDER_C_NONE)) return false;
+    auto at = [&](int k) { return (int)running_[((size_t)(e.y + kCircle[k][1]) * w_ + (size_t)(e.x + kCircle[k][0])) * c_]; };
+    const int candidate = (int)running_[((size_t)e.y * w_ + e.x) * c_];
+    auto cls = [&](int k) { const int v = at(k); return v < candidate - 30 ? 1 : v > candidate + 30 ? 2 : 0; };
+    int d = cls(0) | cls(8);
+    if (d == 0) return false;
+    d &= cls(2) | cls(10);
+    d &= cls(4) | cls(12);
+    d &= cls(6) | cls(14);
+    if (d == 0) return false;
+    d &= cls(1) | cls(9);
+    d &= cls(3) | cls(11);
+    d &= cls(5) | cls(13);
+    d &= cls(7) | cls(15);
+    for (int want = 1; want <= 2; ++want) {
+        if (!(d & want)) continue;
+        int count = 0;
+        for (int k = 0; k < 25; ++k) {
+            if (cls(k & 15) == want) {
+                if (++count == 9) return true;
+            } else {
+                count = 0;
+            }
+        }
+    }
+    return false;
+}
+
+void FeatureTracker::file(uint32_t time, const Event &e, int64_t frames_written) {  // :497-549
+    if (broken_) return;
+    size_t idx = (int64_t)(time / tpf_) >= frames_written ? (size_t)(uint32_t)(time / tpf_ - (uint32_t)frames_written) : 0;
+    if (time % tpf_ == 0 && idx > 0) idx -= 1;
+    if (idx >= features_.size()) {
+        if (features_.empty()) {
+            features_.push_back({(uint64_t)tpf_, {}});
+            features_.push_back({(uint64_t)tpf_ * 2, {}});
+        }
+        const uint64_t new_end_ts = time % tpf_ == 0 ? time : (uint32_t)((time / tpf_ + 1) * tpf_);  // u32 as a release build wraps
+        uint64_t running_end_ts = features_.back().end_ts + tpf_;
+        if (running_end_ts <= new_end_ts && (new_end_ts - running_end_ts) / tpf_ >= (1u << 22)) {
+            broken_ = true;  // (the limit include/adder_framer.h sets)
+            throw FeatureDequePanic("feature interval deque would grow by more than 2^22 intervals");
+        }
+        while (running_end_ts <= new_end_ts) {
+            features_.push_back({running_end_ts, {}});
+            running_end_ts += tpf_;
+        }
+    }
+    if (idx >= features_.size()) {
+        broken_ = true;
+        throw FeatureDequePanic("feature interval index past the deque");
+    }
+    if (features_[idx].end_ts < (uint64_t)time) features_[idx].end_ts = time;
+    features_[idx].features.push_back(Coord{e.x, e.y, e.c});
+}
+
+bool FeatureTracker::ingest_event(Event &event, const std::optional<Event> &last_event, int64_t frames_written) {
+    const uint32_t channel = event.c == ADDER_C_NONE ? 0 : event.c;
+    if (event.x >= w_ || event.y >= h_ || channel >= c_) return false;  // "Silently handle malformed event"
+    const size_t u = ((size_t)event.y * w_ + event.x) * c_ + channel;
+    const uint32_t time = event.t;
+    {   // ingest_event_for_chunk (:984-1133), the trackers
+        const uint64_t prev_running_ts = ts_[u];
+        bool past = false;
+        if (abs_t_) {
+            if (prev_running_ts >= (uint64_t)event.t) past = true;
+            else ts_[u] = event.t;
+        } else {
+            ts_[u] += event.t;
+        }
+        if (!past) {
+            const int64_t q = (int64_t)(ts_[u] ? ts_[u] - 1 : 0) / (int64_t)tpf_;
+            if (q > lastf_[u]) {
+                if (event.d != ADDER_D_EMPTY) {
+                    if (abs_t_ && view_mode_ != 3) {
+                        const uint32_t pr = (uint32_t)prev_running_ts;
+                        event.t = event.t > pr ? event.t - pr : 0;
+                    }
+                    const adder::FramerConsts k = adder::framer_consts(tpf_, ref_interval_, abs_t_, round_up_, view_mode_, source_type_,
+                                                                       practical_d_max_, delta_t_max_, element_);
+                    lasti_[u] = adder::framer_value(event.d, event.t, (uint32_t)ts_[u], (uint32_t)prev_running_ts, k);  // get_frame_value
+                }
+                lastf_[u] = q;
+            }
+            if (round_up_ && ts_[u] % ref_interval_ > 0) ts_[u] = (ts_[u] / ref_interval_ + 1) * ref_interval_;
+        }
+    }
+    if (!detect_features) return false;
+    running_[u] = (uint8_t)(lasti_[u] > 255u ? 255u : lasti_[u]);  // <T as Into<f64>>::into(..) as u8
+    if (last_event && time != last_event->t && is_feature(event)) {
+        file(time, event, frames_written);
+        return true;
+    }
+    return false;
+}
+
+std::optional<FeatureInterval> FeatureTracker::pop_features() {
+    if (features_.empty()) {
+        features_.push_back({(uint64_t)tpf_, {}});
+        features_.push_back({(uint64_t)tpf_ * 2, {}});
+    } else {
+        features_.push_back({(uint64_t)tpf_ + features_.back().end_ts, {}});
+    }
+    FeatureInterval front = std::move(features_.front());
+    features_.pop_front();
+    return front;
 }
 
 // ---------------------------------------------------------------- SimulProcessor (utils/simulproc.rs)

@@ -15,6 +15,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <deque>
 #include <functional>
 #include <memory>
 #include <optional>
@@ -457,6 +458,51 @@ class FramerBuilder {  // driver.rs:36-147
     uint32_t ring_frames_ = 0;
 };
 
+struct Coord {  // lib.rs:216-228
+    uint16_t x, y;
+    uint8_t c;  // ADDER_C_NONE <=> None
+};
+struct FeatureInterval {  // driver.rs:252-257
+    uint64_t end_ts;
+    std::vector<Coord> features;
+};
+struct FeatureDequePanic : std::out_of_range {  // `self.features[idx]` past the deque (driver.rs:544)
+    using std::out_of_range::out_of_range;
+};
+
+// The decode-side feature detection of FrameSequence (driver.rs:482-553, 846-873) as the reference runs it: a serial
+// loop over one mutable plane, entirely on the host -- the trackers of ingest_event_for_chunk (:984-1133; the frames
+// themselves live behind include/adder_framer.h), running_intensities, FAST 9_16 per event (utils/cv.rs:56-212) and the
+// FeatureInterval deque.  The device path (adder_framer_detect_features) is held to this in the tests.
+class FeatureTracker {
+  public:
+    FeatureTracker(PlaneSize plane, uint32_t tpf, uint32_t ref_interval, uint32_t delta_t_max, uint8_t codec_version,
+                   TimeMode time_mode, SourceCamera camera, uint8_t view_mode, uint8_t source_type, float practical_d_max,
+                   uint8_t element);
+    bool detect_features = false;
+    // Framer::ingest_event(&mut event, last_event): event.t is left as ingest_event_for_chunk leaves it (:1022-1028).
+    // Returns true when the event was found to be a feature; throws FeatureDequePanic where the reference panics,
+    // after which nothing more is filed.
+    bool ingest_event(Event &event, const std::optional<Event> &last_event, int64_t frames_written);
+    std::optional<FeatureInterval> pop_features();                                 // :851-873
+    const std::vector<uint8_t> &get_running_intensities() const { return running_; }  // [h][w][c]
+    bool broken() const { return broken_; }
+
+  private:
+    bool is_feature(const Event &e) const;
+    void file(uint32_t time, const Event &e, int64_t frames_written);
+    uint32_t w_, h_, c_, tpf_, ref_interval_, delta_t_max_;
+    bool abs_t_, round_up_;
+    uint8_t view_mode_, source_type_, element_;
+    float practical_d_max_;
+    std::vector<uint64_t> ts_;     // pixel_ts_tracker
+    std::vector<int64_t> lastf_;   // last_filled_tracker
+    std::vector<uint32_t> lasti_;  // last_frame_intensity_tracker
+    std::vector<uint8_t> running_;
+    std::deque<FeatureInterval> features_;
+    bool broken_ = false;
+};
+
 // FrameSequence<T> (driver.rs:261-981), T = u8 / u16 / u32; the per-pixel work runs behind include/adder_framer.h
 class FrameSequence {
   public:
@@ -465,6 +511,14 @@ class FrameSequence {
     FrameSequence(const FrameSequence &) = delete;
     FrameSequence &operator=(const FrameSequence &) = delete;
     bool ingest_event(Event &event);                                          // :437-562 -> frame 0 filled?
+    // the same with the player's last_event: with detection on, the literal serial loop of :482-553 runs on the host
+    // (FeatureTracker) beside the device's framing; event.t is left as the reference leaves it
+    bool ingest_event(Event &event, const std::optional<Event> &last_event);
+    // :401-403.  The host trackers follow the stream from the first detect_features(true) on (the batch paths stay
+    // free of per-event host work until then): switch it on before the first event, and off again if wanted.
+    void detect_features(bool on) { tracker_->detect_features = on; armed_ = armed_ || on; }
+    std::optional<FeatureInterval> pop_features() { return tracker_->pop_features(); }                   // :851-873
+    const std::vector<uint8_t> &get_running_intensities() const { return tracker_->get_running_intensities(); }  // :846-848
     bool ingest_events_events(const std::vector<std::vector<Event>> &events); // :564-626
     bool flush_frame_buffer();                                                // :632-677
     bool is_frame_0_filled();                                                 // :828-843
@@ -482,6 +536,8 @@ class FrameSequence {
     std::vector<uint64_t> seg_offs_;
     std::vector<uint32_t> seen_;
     std::vector<uint8_t> out_;
+    std::unique_ptr<FeatureTracker> tracker_;  // once armed it sees every event, so its trackers equal the device's
+    bool armed_ = false;
 };
 
 // utils/simulproc.rs:33-277 -- transcode a framed source and reconstruct frames from the events

@@ -430,4 +430,84 @@ long long adder_host_encode_events(const AdderEvent *events, size_t n, uint16_t 
         return -1;
     }
 }
+
+// ---- FeatureTracker: FrameSequence's feature detection (driver.rs:482-553, 846-873) as a serial loop on the host; no
+// device is touched.  params = {tps, ref_interval, delta_t_max, codec_version, time_mode, view mode, source type, frame
+// element type, source camera}.
+struct HostFeatures {
+    std::unique_ptr<FeatureTracker> tracker;
+    bool broken = false;
+};
+
+void *adder_host_features_new(uint16_t width, uint16_t height, uint8_t channels, const uint32_t *params, float output_fps,
+                              float practical_d_max) {
+    try {
+        uint32_t tpf = params[1];
+        if (output_fps > 0.0f) {  // (tps as f32 / fps) as u32 (driver.rs:357-361)
+            const float q = (float)params[0] / output_fps;
+            tpf = q >= 4294967296.0f ? 0xffffffffu : (uint32_t)q;
+        }
+        if (!tpf) throw SourceError(SourceError::BadParams, "ticks per output frame is zero");
+        auto *h = new HostFeatures();
+        h->tracker = std::make_unique<FeatureTracker>(PlaneSize(width, height, channels), tpf, params[1], params[2], (uint8_t)params[3],
+                                                      (TimeMode)params[4], (SourceCamera)params[8], (uint8_t)params[5],
+                                                      (uint8_t)params[6], practical_d_max, (uint8_t)params[7]);
+        return h;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return nullptr;
+    }
+}
+void adder_host_features_free(void *h) { delete static_cast<HostFeatures *>(h); }
+void adder_host_features_detect(void *h, int on) { static_cast<HostFeatures *>(h)->tracker->detect_features = on != 0; }
+
+// The player's loop (adder-viz/src/player/adder.rs:409-417) over events[0, n): ingest_event(&mut event, last_event);
+// last_event = Some(event).  *last_valid / *last_t: the last event carried in and out (its t as ingest_event left it).
+// Features are reported as {index_base + i, raw t, x, y} (room for n).  Returns their number.
+long long adder_host_features_ingest(void *hp, const AdderEvent *events, uint64_t n, int *last_valid, uint32_t *last_t,
+                                     long long frames_written, uint64_t index_base, AdderFramerFeature *out) {
+    HostFeatures *h = static_cast<HostFeatures *>(hp);
+    long long count = 0;
+    std::optional<Event> last;
+    if (*last_valid) {
+        Event e{};
+        e.t = *last_t;
+        last = e;
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        Event e = events[i];
+        bool found = false;
+        try {
+            found = h->tracker->ingest_event(e, last, frames_written);
+        } catch (const FeatureDequePanic &) {
+            h->broken = true;  // the feature was found, the reference panics while filing it
+            found = true;
+        }
+        if (found) out[count++] = AdderFramerFeature{index_base + i, events[i].t, events[i].x, events[i].y};
+        last = e;
+    }
+    *last_valid = last ? 1 : 0;
+    *last_t = last ? last->t : 0u;
+    return count;
+}
+
+// pop_features: 0, or 1 once a feature could not be filed (nothing is popped then), or 2 when the popped interval holds
+// more than the cap coordinates copied (*count is their number)
+int adder_host_features_pop(void *hp, uint64_t *end_ts, uint16_t *xy, uint32_t cap, uint32_t *count) {
+    HostFeatures *h = static_cast<HostFeatures *>(hp);
+    if (h->broken || h->tracker->broken()) return 1;
+    const std::optional<FeatureInterval> iv = h->tracker->pop_features();
+    *end_ts = iv->end_ts;
+    *count = (uint32_t)iv->features.size();
+    for (size_t k = 0; k < iv->features.size() && k < cap; ++k) {
+        xy[2 * k] = iv->features[k].x;
+        xy[2 * k + 1] = iv->features[k].y;
+    }
+    return iv->features.size() > cap ? 2 : 0;
+}
+
+void adder_host_features_plane(void *hp, uint8_t *out) {
+    const std::vector<uint8_t> &p = static_cast<HostFeatures *>(hp)->tracker->get_running_intensities();
+    memcpy(out, p.data(), p.size());
+}
 }

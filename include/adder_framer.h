@@ -18,8 +18,11 @@
  * switch: the reference stores the mode (driver.rs:270, 383) and never reads it, both modes ingest alike.
  * Frame element types: u8, and u16 / u32 (<u16 / u32 as FrameValue>, scale_intensity.rs:111-209) whose frames are popped
  * as the big-endian bincode bytes the reference's writers produce (driver.rs:279,395-398,944).  FrameSequence<u64> cannot
- * be instantiated in the reference (its methods need T: Into<f64>).  Not built: EventCoordless frames, feature detection
- * on frames, buffer_limit.
+ * be instantiated in the reference (its methods need T: Into<f64>).  Not built: EventCoordless frames, buffer_limit.
+ *
+ * Feature detection while framing (FramerBuilder::detect_features / Framer::detect_features /
+ * FrameSequence::pop_features / ::get_running_intensities, driver.rs:48, 140-144, 172, 252-257, 271-275, 401-403,
+ * 482-553, 846-873): the adder_framer_detect_features block below.
  */
 #ifndef ADDER_FRAMER_H
 #define ADDER_FRAMER_H
@@ -113,6 +116,63 @@ int adder_framer_write_frame(AdderFramer *fr, uint8_t *out);
 /* flush_frame_buffer: if any pixel has reached beyond frame 0, fill frame 0's missing pixels with their
  * last intensity (*frame0_ready = 1); the frame must be popped before the next ingest. */
 int adder_framer_flush(AdderFramer *fr, int *frame0_ready);
+
+/* ---- Feature detection while framing (Framer::ingest_event with detect_features on, driver.rs:482-553) ----
+ *
+ * With detection on, every event of an ingest call writes running_intensities[y][x][c] = the unit's last frame
+ * intensity `as u8` (saturating), and an event whose t differs from the previous event's t -- the t
+ * ingest_event_for_chunk LEFT in that event, driver.rs:1022-1028 -- is tested with FAST 9_16 (utils/cv.rs:56-212) on
+ * the plane as it stands at that moment, when it is on channel 0 / None and 3 pixels off the border.  Stream order is
+ * the order of the call's event array, across segments.
+ *
+ * All ingest entry points detect.  With detection on they take the same route: the whole range
+ * [offsets[0], offsets[n]) is sorted by pixel-channel on the device (so the per-segment contiguity rule does not apply),
+ * framed and tested; adder_framer_ingest_frames_device* do not use their tile kernel then, and
+ * adder_framer_ingest_frames_device_offsets reads the two ends of its offsets back (it waits for the stream).  With
+ * detection off every entry point launches what it launched before this block existed.  A call takes fewer than 2^31
+ * events with detection on.
+ *
+ * The previous event is carried from call to call (the player's `last_event`), as {valid, t}; it is updated by calls
+ * made with detection on only and cleared by adder_framer_reset_last_event.  Any split of a stream into calls, with
+ * no pop in between, gives the features of one call (indices shifted) and the same plane.
+ */
+typedef struct AdderFramerFeature {
+    uint64_t index; /* of the event in the call's event array */
+    uint32_t t;     /* event.t as it arrived (`time`, driver.rs:446) */
+    uint16_t x, y;
+} AdderFramerFeature;
+
+/* Framer::detect_features.  May be switched between any two calls.  ADDER_E_BAD_PARAMS on a context that owns a row
+ * band: the ring reaches 3 rows over. */
+int adder_framer_detect_features(AdderFramer *fr, int on);
+/* Allocates what calls of up to max_events events need with detection on (about 44 bytes per event: sort keys and
+ * indices twice, per-event intensities and times, marks, offsets, 16 bytes per possible feature), so that those calls
+ * neither allocate nor wait.  Without it the buffers grow in the first call that needs them. */
+int adder_framer_reserve_features(AdderFramer *fr, uint64_t max_events);
+/* `last_event = None` (adder-viz/src/player/adder.rs:409) */
+int adder_framer_reset_last_event(AdderFramer *fr);
+
+/* The features of the last ingest call, in stream order.  *count is their number; when it exceeds `capacity` nothing is
+ * copied and nothing changes (ADDER_E_OUT_CAPACITY): call again with room for *count.  Both wait for the call.
+ * _device copies into device memory on `stream`. */
+int adder_framer_features(AdderFramer *fr, AdderFramerFeature *out, uint64_t capacity, uint64_t *count);
+int adder_framer_features_device(AdderFramer *fr, AdderFramerFeature *d_out, uint64_t capacity, uint64_t *count,
+                                 void *stream);
+
+/* FrameSequence::pop_features (driver.rs:851-873): the front FeatureInterval, its coordinates as {x, y} pairs
+ * (channel 0 / None by construction).  The deque bookkeeping of driver.rs:497-549 runs on the host, with the
+ * frames_written the context had during each ingest call.  *count exceeding `capacity`: ADDER_E_OUT_CAPACITY, nothing
+ * changes.  Where the reference would index past the deque and panic (a feature whose interval the deque does not
+ * reach even after growing, e.g. after more pop_features than popped frames), or would grow it by more than 2^22
+ * intervals for one feature, that feature and every later one is not filed and every pop_features from then on
+ * reports ADDER_E_BAD_PARAMS; framing goes on.  The reference's u32 arithmetic on `time` wraps as its release build
+ * does. */
+int adder_framer_pop_features(AdderFramer *fr, uint64_t *end_ts, uint16_t *xy, uint32_t capacity, uint32_t *count);
+
+/* FrameSequence::get_running_intensities: the [height][width][channels] u8 plane.  Zeros at create, kept across calls,
+ * changed only by calls made with detection on. */
+int adder_framer_running_intensities(AdderFramer *fr, uint8_t *out);
+int adder_framer_running_intensities_device(AdderFramer *fr, uint8_t *d_out, void *stream);
 
 #ifdef __cplusplus
 }
