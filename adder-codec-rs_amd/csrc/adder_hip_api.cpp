@@ -1623,6 +1623,9 @@ extern "C" int adder_hip_integrate_device(AdderHipCtx *c, const uint8_t *d_frame
     if (c->f_submitted != c->f_collected)
         return fail(c, ADDER_E_BAD_PARAMS, "frames are in flight (call adder_hip_frame_collect)");
     if (!d_frames || !d_frame_offsets || (!d_out && out_cap)) return fail(c, ADDER_E_BAD_PARAMS, "null pointer");
+    // AdderEvents leave as dwords (every expansion); wire records are bytes and may start anywhere (include/adder_hip.h)
+    if (!c->wire_batch && ((uintptr_t)d_out & 3u) != 0u)
+        return fail(c, ADDER_E_BAD_PARAMS, "d_out must be 4-byte aligned (AdderEvent alignment)");
     if (!(time_spanned >= 0.0f)) return fail(c, ADDER_E_BAD_PARAMS, "time_spanned must be >= 0");
     { int rc_ = band_precheck(c, num_frames); if (rc_ != ADDER_OK) return rc_; }
     HIPCHK(c, hipSetDevice(c->device));
@@ -2128,6 +2131,7 @@ extern "C" int adder_hip_wire_events_device(AdderHipCtx *c, const AdderEvent *d_
     if (!c) return ADDER_E_BAD_PARAMS;
     if (n_bytes) *n_bytes = 0;
     if ((!d_events || !d_out) && n_events) return fail(c, ADDER_E_BAD_PARAMS, "null device buffer");
+    if (((uintptr_t)d_events & 3u) != 0u) return fail(c, ADDER_E_BAD_PARAMS, "d_events must be 4-byte aligned (AdderEvent alignment)");
     const size_t need = n_events * wire_record_bytes(c);
     if (n_bytes) *n_bytes = need;
     if (need > out_cap_bytes) return fail(c, ADDER_E_OUT_CAPACITY, "wire buffer too small: need %zu bytes", need);

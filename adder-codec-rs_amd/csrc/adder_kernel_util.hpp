@@ -156,6 +156,18 @@ __device__ __forceinline__ void gstore_ev(void *base, uint32_t byte_off, V v) {
     if (ADDER_NT_EVENTS) gstore_nt<V>(base, byte_off, v);
     else gstore<V>(base, byte_off, v);
 }
+// The same through a pointer of ANY byte alignment (wire records in the caller's buffer): global memory takes a dword, or
+// four, at any address -- the same instructions --, but the type has to say so, or the compiler may assume the low address
+// bits are zero.
+template <class V>
+__device__ __forceinline__ void gstore_ev_any(void *base, uint32_t byte_off, V v) {
+    typedef typename RawOf<sizeof(V)>::type R;
+    typedef R __attribute__((aligned(1))) RA;
+    R r;
+    __builtin_memcpy(&r, &v, sizeof(V));
+    if (ADDER_NT_EVENTS) __builtin_nontemporal_store(r, reinterpret_cast<ADDER_GLOBAL RA *>((ADDER_GLOBAL char *)base + byte_off));
+    else *reinterpret_cast<ADDER_GLOBAL RA *>((ADDER_GLOBAL char *)base + byte_off) = r;
+}
 template <class V>
 __device__ __forceinline__ V gload_rec(const void *base, uint32_t byte_off) {
     if (ADDER_NT_RECLOAD) return gload_nt<V>(base, byte_off);

@@ -2503,27 +2503,35 @@ __device__ __forceinline__ uint32_t coord_xy_c(const UnitCoord &uc, uint32_t uni
 // The wave's staging buffer -> the stream.  xb[phase .. phase + 3 n) holds n events whose first dword
 // goes to dword `gd0` of the output (phase == gd0 & 3, so 16-byte blocks of the buffer are 16-byte
 // blocks of the destination).  Uniform arguments; returns nothing, the caller resets its fill.
+template <bool ANY = false>
 __device__ __forceinline__ void xbuf_flush_dwords(const uint32_t *xb, uint32_t phase, uint32_t nd, uint32_t *out_dw,
                                                   uint64_t gd0, uint32_t lane);
 __device__ __forceinline__ void xbuf_flush(const uint32_t *xb, uint32_t phase, uint32_t n, uint32_t *out_dw,
                                            uint64_t gd0, uint32_t lane) {
     xbuf_flush_dwords(xb, phase, n * 3u, out_dw, gd0, lane);
 }
-// xb[phase .. phase + nd) -> dwords [gd0, gd0 + nd) of the output, phase == gd0 & 3
+// xb[phase .. phase + nd) -> dwords [gd0, gd0 + nd) of the output, phase == gd0 & 3.  out_dw: AdderEvents, 4-byte aligned
+// (16-byte blocks of the buffer are 16-byte blocks of a 16-byte aligned destination; any other takes the same stores);
+// ANY: wire records, out_dw is the caller's byte pointer -- the dwords lie at whatever address that makes them.
+template <bool ANY>
 __device__ __forceinline__ void xbuf_flush_dwords(const uint32_t *xb, uint32_t phase, uint32_t nd, uint32_t *out_dw,
                                                   uint64_t gd0, uint32_t lane) {
+    auto put = [](void *base, uint32_t byte_off, auto v) {
+        if constexpr (ANY) gstore_ev_any<decltype(v)>(base, byte_off, v);
+        else gstore_ev<decltype(v)>(base, byte_off, v);
+    };
     uint32_t head = (4u - phase) & 3u;
     head = head < nd ? head : nd;
-    uint32_t *const dst = out_dw + gd0;  // uniform 64-bit base; the lanes add 32-bit offsets
-    if (lane < head) gstore_ev<uint32_t>(dst, lane * 4u, xb[phase + lane]);
+    uint8_t *const dst = reinterpret_cast<uint8_t *>(out_dw) + gd0 * 4u;  // uniform 64-bit base; the lanes add 32-bit offsets
+    if (lane < head) put(dst, lane * 4u, xb[phase + lane]);
     const uint32_t body = (nd - head) >> 2;  // whole 16-byte blocks
     const uint32_t b0 = phase + head;        // a multiple of 4
     for (uint32_t k = lane; k < body; k += kWave) {
         const uint4 v = *reinterpret_cast<const uint4 *>(xb + b0 + 4u * k);
-        gstore_ev<uint4>(dst, (head + 4u * k) * 4u, v);
+        put(dst, (head + 4u * k) * 4u, v);
     }
     const uint32_t tail = (nd - head) & 3u;
-    if (lane < tail) gstore_ev<uint32_t>(dst, (head + 4u * body + lane) * 4u, xb[b0 + 4u * body + lane]);
+    if (lane < tail) put(dst, (head + 4u * body + lane) * 4u, xb[b0 + 4u * body + lane]);
 }
 
 // The same straight into the raw sink's records (RawOutput::ingest_event, raw/stream.rs:101-120: bincode fixint big-endian;
@@ -2620,7 +2628,7 @@ __device__ __forceinline__ void xbuf_flush_wire(const uint32_t *xb, uint32_t pad
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    xbuf_flush_dwords(xb, q0, body * rec, reinterpret_cast<uint32_t *>(out), gd0, lane);
+    xbuf_flush_dwords<true>(xb, q0, body * rec, reinterpret_cast<uint32_t *>(out), gd0, lane);  // (`out` may be any byte address)
 }
 // where the first staged event goes in the LDS buffer (dwords): events -> the 16-byte phase of its destination; wire
 // records -> so that the first event whose stream index is a multiple of four lies on a 16-byte boundary
@@ -3122,7 +3130,8 @@ extern "C" hipError_t adder_launch_expand_bands(const uint8_t *descs, uint32_t s
 // records otherwise.  The host then writes the bytes as they are (and D2H moves 9 instead of
 // 12 bytes per event).  A workgroup converts kWireEvents events: coalesced dword loads into
 // LDS, per-event repack in LDS, coalesced dword stores of the record bytes (kWireEvents is a
-// multiple of 4, so every workgroup's output starts dword-aligned).
+// multiple of 4, so every workgroup's output starts on a dword of the stream; `out` itself may be
+// any byte address: the store's type says so).
 // ------------------------------------------------------------------------------------------
 constexpr uint32_t kWireEvents = 1024;
 __global__ __launch_bounds__(256) void adder_wire_kernel(const uint32_t *__restrict__ ev, uint64_t n, uint32_t rec,
@@ -3169,7 +3178,8 @@ __global__ __launch_bounds__(256) void adder_wire_kernel(const uint32_t *__restr
             o |= byte << (8u * j);
         }
         if (4u * k + 4u <= bytes) {
-            reinterpret_cast<uint32_t *>(dst)[k] = o;
+            typedef uint32_t __attribute__((aligned(1))) u32_any;
+            *reinterpret_cast<u32_any *>(dst + 4u * k) = o;
         } else {  // the stream's last, partial dword
             for (uint32_t j = 0; 4u * k + j < bytes; ++j) dst[4u * k + j] = (uint8_t)(o >> (8u * j));
         }

@@ -393,7 +393,7 @@ constexpr uint32_t kLpxRecCap = ADDER_LPX_REC_CAP;
 #endif
 constexpr uint32_t kLpxWaves = ADDER_LPX_WAVES;  // waves (= items) per workgroup: they share nothing
 constexpr uint32_t kLpxStageEvents = ADDER_LPX_STAGE_EVENTS;
-static_assert(kLpxPairs == 8u && kLpxRecCap >= kLpPairUnits && kLpxRecCap % kWave == 0u && kLpxStageEvents >= 6u * kWave && kLpxStageEvents % 16u == 0u, "sizes the loops below assume");
+static_assert(kLpxPairs == 8u && kLpxPairs * kLpPairUnits == kLpxWaveUnits && kLpxRecCap >= kLpPairUnits && kLpxRecCap % kWave == 0u && kLpxStageEvents >= 6u * kWave && kLpxStageEvents % 16u == 0u, "sizes the loops below assume");
 
 // What adder_lpx_kernel takes by value: what stays the same for every batch of a context's current scratch ring.
 struct LpxArgs {
@@ -518,16 +518,8 @@ __device__ __forceinline__ void lpx_wave(const BatchArgs *__restrict__ b, const 
     const uint32_t rowlen = x.rowlen;
     const bool rgb = x.channels == 3u;
     const float inv_row = x.inv_row;
-    uint32_t y0;
-    {   // seg0 * 128 / rowlen: a float estimate (units stay below 2^26), fixed either way
-        const uint32_t u = seg0 * kWaveUnits;
-        uint32_t q = (uint32_t)((float)u * inv_row);
-        q -= (q != 0u && q * rowlen > u) ? 1u : 0u;
-        q -= (q != 0u && q * rowlen > u) ? 1u : 0u;
-        q += (q + 1u) * rowlen <= u ? 1u : 0u;
-        q += (q + 1u) * rowlen <= u ? 1u : 0u;
-        y0 = __builtin_amdgcn_readfirstlane(q);
-    }
+    // seg0 * 128 / rowlen (adder_pixel.hpp lpx_row0: a float estimate -- units stay below 2^26 --, fixed either way)
+    const uint32_t y0 = __builtin_amdgcn_readfirstlane(lpx_row0(seg0 * kWaveUnits, rowlen, inv_row));
     const uint32_t rem0 = seg0 * kWaveUnits - y0 * rowlen;
     const uint32_t yb = y0 + x.row_begin;
     const uint32_t wraps = x.wraps;
@@ -663,23 +655,8 @@ __device__ __forceinline__ void lpx_wave(const BatchArgs *__restrict__ b, const 
             // coordinates: the unit counted from the wave's first
             uint32_t rem = rem0 + ((rec.x >> 28) << 8) + (w8 & 0xffu);
             uint32_t y = yb;
-            if (wraps != 0u) {  // at most two rows further on: min(rem, rem - rowlen) is rem - rowlen exactly when that does not wrap
-                y += (rem >= rowlen ? 1u : 0u) + (rem >= 2u * rowlen ? 1u : 0u);
-                rem = min(rem, rem - rowlen);
-                rem = min(rem, rem - rowlen);
-            } else {  // narrow planes: a quotient estimate, one step either way
-                uint32_t q = (uint32_t)((float)rem * inv_row);
-                q -= q * rowlen > rem ? 1u : 0u;
-                q += (q + 1u) * rowlen <= rem ? 1u : 0u;
-                rem -= q * rowlen;
-                y += q;
-            }
-            uint32_t x = rem;
-            r.c = 0xffu;
-            if (rgb) {
-                x = (uint32_t)(((uint64_t)rem * 0xAAAAAAABull) >> 33);  // rem / 3
-                r.c = rem - 3u * x;
-            }
+            lpx_unit_row(rem, y, rowlen, inv_row, wraps);  // (adder_pixel.hpp: by comparison on wide planes, by division on narrow ones)
+            const uint32_t x = lpx_x_c(rem, rgb, r.c);
             r.xy = x | (y << 16);
             r.xyw = __builtin_amdgcn_perm(0u, r.xy, 0x02030001u);  // x_hi x_lo y_hi y_lo
             return r;
@@ -789,7 +766,7 @@ extern "C" hipError_t adder_launch_lpx(const BatchArgs *b, const BatchArgs *hb, 
     x.rowlen = hb->base.rowlen;
     x.channels = hb->base.channels;
     x.row_begin = hb->base.row_begin;
-    x.wraps = x.rowlen >= kLpxPairs * kLpPairUnits ? 1u : x.rowlen >= kLpxPairs * kLpPairUnits / 2u ? 2u : 0u;  // (0: divide)
+    x.wraps = lpx_wraps(x.rowlen);  // (0: divide)
     x.inv_row = 1.0f / (float)x.rowlen;
     const uint32_t per_block = kLpxWaves * kExpandSegs;  // segments per block
     const dim3 grid((num_waves + per_block - 1u) / per_block, nf), block(kLpxWaves * kWave);

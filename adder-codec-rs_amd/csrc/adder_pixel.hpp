@@ -1621,6 +1621,51 @@ ADDER_HD void lp_unpark4(uint32_t w4, uint32_t esc, uint32_t &w0, uint32_t &w8) 
     w0 = lp_escapes(w4) ? esc : w4 >> kLpRhoShift;
     w8 = w4 & 0xffffffu;
 }
+// adder_lpx_kernel's COORDINATES.  A wave expands kLpxWaveUnits consecutive units of one frame; a record names its unit by
+// the pair inside the wave and the unit inside the pair, so (x, y, c) come from the wave's first unit u0 = (y0, rem0) and
+// an offset below kLpxWaveUnits.  rowlen = width * channels, inv_row = 1.0f / (float)rowlen, units stay below 2^26.
+// (tests/test_device_logic_cpu.py runs these against 64-bit division for every row length a plane can have.)
+constexpr uint32_t kLpxWaveUnits = 2048u;
+// how a unit's row is found: 1 = by comparison (rowlen >= 1024: a wave's units span at most three rows), 0 = by division.
+// (TWO ways; the division is right for every row length -- the comparison saves its float quotient on wide planes.)
+ADDER_HD uint32_t lpx_wraps(uint32_t rowlen) { return rowlen >= kLpxWaveUnits / 2u ? 1u : 0u; }
+// u / rowlen for the wave's first unit u: a float estimate, fixed either way
+ADDER_HD uint32_t lpx_row0(uint32_t u, uint32_t rowlen, float inv_row) {
+    uint32_t q = (uint32_t)((float)u * inv_row);
+    q -= (q != 0u && q * rowlen > u) ? 1u : 0u;
+    q -= (q != 0u && q * rowlen > u) ? 1u : 0u;
+    q += (q + 1u) * rowlen <= u ? 1u : 0u;
+    q += (q + 1u) * rowlen <= u ? 1u : 0u;
+    return q;
+}
+// rem = rem0 + the unit's offset in the wave (< rowlen + kLpxWaveUnits), y = the wave's first row: -> the unit's own row
+// and its offset in that row
+ADDER_HD void lpx_unit_row(uint32_t &rem, uint32_t &y, uint32_t rowlen, float inv_row, uint32_t wraps) {
+    if (wraps != 0u) {  // at most two rows further on: min(rem, rem - rowlen) is rem - rowlen exactly when that does not wrap
+        y += (rem >= rowlen ? 1u : 0u) + (rem >= 2u * rowlen ? 1u : 0u);
+        uint32_t t = rem - rowlen;
+        rem = rem < t ? rem : t;
+        t = rem - rowlen;
+        rem = rem < t ? rem : t;
+    } else {  // narrow planes: a quotient estimate, one step either way
+        uint32_t q = (uint32_t)((float)rem * inv_row);
+        q -= q * rowlen > rem ? 1u : 0u;
+        q += (q + 1u) * rowlen <= rem ? 1u : 0u;
+        rem -= q * rowlen;
+        y += q;
+    }
+}
+// the offset in the row -> x (and the channel, 0xff on a one-channel plane)
+ADDER_HD uint32_t lpx_x_c(uint32_t rem, bool rgb, uint32_t &c) {
+    uint32_t x = rem;
+    c = 0xffu;
+    if (rgb) {
+        x = (uint32_t)(((uint64_t)rem * 0xAAAAAAABull) >> 33);  // rem / 3
+        c = rem - 3u * x;
+    }
+    return x;
+}
+
 // (base_val, rho) of unit j after nb frames of the launch
 ADDER_HD LrPx lp_final(const LpWord &s, uint32_t j, uint32_t nb) {
     LrPx p;

@@ -248,7 +248,9 @@ int adder_hip_integrate_batch(AdderHipCtx *ctx, const uint8_t *frames_hwc, uint3
                               uint64_t *frame_offsets);
 
 /* --- T frames resident in HBM (clip and event buffer are DEVICE pointers) -----------
- * d_frames: packed [T][rows][width][channels] u8.  d_out: device AdderEvent[out_cap].
+ * d_frames: packed [T][rows][width][channels] u8.  d_out: device AdderEvent[out_cap], 4-byte aligned as
+ * the type says (the events leave as dwords) -- any other address is refused with
+ * ADDER_E_BAD_PARAMS before anything is queued, the context unchanged.
  * d_frame_offsets: device uint64[T+1] (prefix offsets into d_out; [0] = 0).
  * stream: hipStream_t.  NULL = the context's own (non-blocking) stream, ordered BEHIND whatever the caller has queued on the
  * legacy default stream so far (a NULL stream means "the default stream" to the caller: buffers it prepared there -- zeroed,
@@ -264,7 +266,9 @@ int adder_hip_integrate_device(AdderHipCtx *ctx, const uint8_t *d_frames, uint32
  * raw .adder file's header and its EOF event, in HBM, without a second pass (and 25 % fewer bytes than AdderEvents).
  * d_frame_offsets counts EVENTS as for adder_hip_integrate_device (frame f's records start at byte
  * d_frame_offsets[f] * record_bytes); wire_cap_bytes / record_bytes is the capacity in events, with the same overflow
- * semantics (adder_hip_finish reports the size needed and rolls back).  Dense FramePerfect batches without feature mode. */
+ * semantics (adder_hip_finish reports the size needed and rolls back).  Dense FramePerfect batches without feature mode.
+ * d_wire is a byte stream and may start at ANY byte address, whichever kernels the batch runs: nothing in front of d_wire
+ * and nothing from byte (wire_cap_bytes / record_bytes) * record_bytes on is written. */
 int adder_hip_integrate_wire_device(AdderHipCtx *ctx, const uint8_t *d_frames, uint32_t num_frames, float time_spanned,
                                     uint8_t *d_wire, size_t wire_cap_bytes, uint64_t *d_frame_offsets, void *stream);
 /* Waits for the work queued by adder_hip_integrate_device and reports its status;
@@ -437,7 +441,8 @@ int adder_hip_reset(AdderHipCtx *ctx);
  * Header and EOF stay on the host (adder_raw_header / adder_raw_eof).
  *
  * adder_hip_wire_events_device: `n_events` events of this context at d_events -> d_out (device
- * memory), asynchronously on `stream`; *n_bytes = n_events * 9 (or 11).
+ * memory), asynchronously on `stream`; *n_bytes = n_events * 9 (or 11).  d_out may start at any byte address; d_events
+ * is 4-byte aligned as its type says (ADDER_E_BAD_PARAMS otherwise, nothing queued).
  * adder_hip_integrate_batch_raw: adder_hip_integrate_batch with the serialisation appended; out_bytes
  * (host memory, pinned for full speed) receives the records of all T frames in stream order;
  * frame_offsets (optional, T+1) are EVENT indices as in adder_hip_integrate_batch. */

@@ -986,6 +986,44 @@ extern "C" uint64_t sim_fast_div_check(uint32_t d, const uint32_t *n, size_t cou
     return bad;
 }
 
+// adder_lpx_kernel's coordinates (adder_pixel.hpp lpx_wraps / lpx_row0 / lpx_unit_row / lpx_x_c, as lpx_wave calls them)
+// against 64-bit division, for ONE row length: every wave start u = 2048 k below 2^26 whose row fits 16 bits -- all k up to
+// 64, every 97th beyond --, every unit offset of the wave (as far as its row fits 16 bits), both channel counts.
+// Returns the number of mismatches; *checked counts the (wave, offset) points, bad[0..4) describes the first mismatch.
+extern "C" uint64_t sim_lpx_coords_check(uint32_t rowlen, uint32_t row_begin, uint64_t *checked, uint32_t *bad) {
+    using namespace adder;
+    const float inv_row = 1.0f / (float)rowlen;  // (adder_launch_lpx)
+    const uint32_t wraps = lpx_wraps(rowlen);
+    uint64_t n_bad = 0, n = 0;
+    auto report = [&](uint32_t u, uint32_t off, uint32_t got, uint32_t want) {
+        if (n_bad++ == 0) { bad[0] = u; bad[1] = off; bad[2] = got; bad[3] = want; }
+    };
+    for (uint64_t k = 0; k * kLpxWaveUnits < (1ull << 26); k += k < 64 ? 1 : 97) {
+        const uint32_t u = (uint32_t)(k * kLpxWaveUnits);
+        const uint64_t y_ref = (uint64_t)u / rowlen;
+        if (y_ref > 65535u) break;
+        const uint32_t y0 = lpx_row0(u, rowlen, inv_row);
+        if (y0 != y_ref) { report(u, ~0u, y0, (uint32_t)y_ref); continue; }
+        const uint32_t rem0 = u - y0 * rowlen, yb = y0 + row_begin;
+        uint64_t yr = y_ref, rr = (uint64_t)u % rowlen;  // the reference: (u + off) / rowlen and (u + off) % rowlen, by walking
+        uint32_t off = 0;
+        for (; off < kLpxWaveUnits && yr <= 65535u; ++off) {
+            uint32_t rem = rem0 + off, y = yb;
+            lpx_unit_row(rem, y, rowlen, inv_row, wraps);
+            uint32_t c1, c3;
+            const uint32_t x1 = lpx_x_c(rem, false, c1), x3 = lpx_x_c(rem, true, c3);
+            if (y != yr + row_begin || rem != rr || x1 != rr || c1 != 0xffu || x3 != rr / 3u || c3 != rr % 3u)
+                report(u, off, rem | (y << 16), (uint32_t)(rr | ((yr + row_begin) << 16)));
+            ++n;
+            if (++rr == rowlen) { rr = 0; ++yr; }
+        }
+        // (the walk is the division: checked where it ends)
+        if (yr != ((uint64_t)u + off) / rowlen || rr != ((uint64_t)u + off) % rowlen) report(u, off, (uint32_t)rr, ~0u);
+    }
+    *checked = n;
+    return n_bad;
+}
+
 static uint32_t g_view_mode = 0, g_source_type = 0, g_view_dtm = 0, g_value_type = 0;
 static float g_practical_d_max = 0.0f;
 // what the next sim_framer_run shows (FramedViewMode / SourceType; 0, 0 = the U8 Intensity view)

@@ -914,3 +914,34 @@ def test_lr_quiet_groups_break_at_every_position(time_mode):
             assert rc == 0 and len(want) == len(got) and np.array_equal(want, got), (groups_on, k, nb)
             k += nb
         assert (sv.quiet_groups[0] > 0.8 * frames * H * W / 16) == groups_on
+
+
+def test_lpx_coordinates_against_division_for_every_row_length():
+    """adder_lpx_kernel takes (x, y, c) of a record from its wave's first unit -- a float estimate of u / rowlen with
+    fix-ups -- and the unit's offset in the wave, by comparison (rowlen >= 1024: at most three rows in a wave) or by a second
+    float estimate (below that).  The functions the kernel calls (adder_pixel.hpp lpx_wraps / lpx_row0 / lpx_unit_row /
+    lpx_x_c), compiled for the host: every rowlen in 1..6200 and 65535, 3 x 65535; every wave start 2048 k below 2^26 whose
+    row fits 16 bits (all k up to 64, every 97th beyond); all 2048 unit offsets; one and three channels -- against
+    u / rowlen and u % rowlen in 64-bit integers."""
+    import ctypes as C
+    import sim_py
+    L = sim_py.lib()
+    L.sim_lpx_coords_check.restype = C.c_uint64
+    L.sim_lpx_coords_check.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    from concurrent.futures import ThreadPoolExecutor
+
+    def one(rowlen):  # (the call leaves the interpreter lock: row lengths are checked side by side)
+        checked, bad = C.c_uint64(0), (C.c_uint32 * 4)()
+        n_bad = L.sim_lpx_coords_check(rowlen, 0, C.byref(checked), bad)
+        assert n_bad == 0, (rowlen, n_bad, list(bad))
+        # every start is there: 2^26 / 2048 waves or as many as 65536 rows hold, and whole waves but for the last rows
+        starts = min(1 << 15, (65536 * rowlen + 2047) // 2048)
+        assert checked.value >= 2048 * (min(starts, 65) - 1), (rowlen, checked.value)
+        return checked.value
+
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+        total = sum(pool.map(one, list(range(1, 6201)) + [65535, 3 * 65535]))
+    assert total > 4_000_000_000
+    for rowlen, row_begin in ((1025, 5), (2049, 3), (700, 11)):  # a row band: row_begin is added to every row
+        checked, bad = C.c_uint64(0), (C.c_uint32 * 4)()
+        assert L.sim_lpx_coords_check(rowlen, row_begin, C.byref(checked), bad) == 0, (rowlen, list(bad))

@@ -1,5 +1,6 @@
 """A fixed-seed slice of tools/fuzz_parity.py in the GPU suite: random small planes, contents, modes, qualities, batch
-lengths and launch depths, with rollbacks -- the HIP path against the oracle, bit-exact."""
+lengths and launch depths, with rollbacks, through host events, device events or wire records -- the HIP path against the
+oracle, bit-exact."""
 import os
 import sys
 
@@ -15,8 +16,11 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 def test_randomised_parity_soak(seed):
     import fuzz_parity
     rng = np.random.default_rng(1000 + seed)
+    fuzz_parity.STATS.clear()
     units = sum(fuzz_parity.one(rng) for _ in range(120))
     assert units > 0
+    # every seed reaches all three output forms (host events, device events, wire records) and the wide plane
+    assert all(fuzz_parity.STATS.get(k, 0) > 0 for k in ("form:host", "form:device", "form:wire", "W:1100")), fuzz_parity.STATS
 
 
 @pytest.mark.gpu

@@ -1,7 +1,9 @@
 """Randomised GPU-vs-oracle parity soak (not a test: run it for as long as you like on the GPU box).
 Small planes, contents that mix static stretches, jitter inside and outside the contrast band, black regions, scene cuts and
 noise; Collapse / Normal, DeltaT / AbsoluteT, delta_t_max 255 / 1020 / 7650, crf 0 / 3 / 6 / 9 numbers, gray / RGB, random batch
-lengths and launch depths, some batches with an event buffer that is too small (rollback + retry).
+lengths and launch depths, some batches with an event buffer that is too small (rollback + retry).  A clip goes through one of
+three output forms, chosen at random: AdderEvents in host memory (integrate_batch), AdderEvents in HBM (integrate_device), the
+raw sink's records in HBM (integrate_wire_device, against the oracle's raw sink byte for byte).
 usage: python tools/fuzz_parity.py [seconds] [seed]   (FUZZ_CRF0=1: crf 0 only; FUZZ_CONTINUOUS=0/1)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,6 +13,35 @@ import adder_amd as A
 from oracle import oracle as O
 
 CRF = {0: (0, 0, 10), 3: (2, 7, 7), 6: (7, 13, 4), 9: (15, 25, 1)}
+STATS = {}  # what one() has reached so far: "form:<name>", "W:<width>" -> clips
+
+def device_batch(hv, frames, per, C, form, small):
+    """One batch through integrate_device / integrate_wire_device into a buffer of exactly its size (`small`: half of it first --
+    reported with the size needed, rolled back) with sentinel bytes behind it; returns whether bytes and offsets are the oracle's."""
+    import torch
+    nb, want = len(frames), np.concatenate(per)
+    rec = 12 if form == "device" else (9 if C == 1 else 11)
+    ref = want.tobytes() if form == "device" else O.raw_events(want, C)
+    st = torch.cuda.current_stream().cuda_stream
+    d_frames = torch.from_numpy(np.ascontiguousarray(frames).reshape(nb, -1)).cuda()
+    d_out = torch.full((len(want) * rec + 48,), 0xAB, dtype=torch.uint8, device="cuda")
+    d_offs = torch.zeros(nb + 1, dtype=torch.int64, device="cuda")
+    submit = hv.integrate_device if form == "device" else hv.integrate_wire_device
+    if small:
+        submit(d_frames, d_out[:(len(want) // 2) * rec], d_offs, stream=st)
+        try:
+            hv.finish()
+            raise SystemExit("overflow not reported")
+        except A.AdderHipError as e:
+            assert e.code == A.E_OUT_CAPACITY and hv.last_required == len(want), (e.code, hv.last_required, len(want))
+        if not bool((d_out[(len(want) // 2) * rec:] == 0xAB).all()):
+            return False
+    submit(d_frames, d_out[:len(want) * rec], d_offs, stream=st)
+    if hv.finish() != len(want):
+        return False
+    got = d_out.cpu().numpy()
+    offs = np.concatenate([[0], np.cumsum([len(p) for p in per])])
+    return got[:len(ref)].tobytes() == ref and bool((got[len(ref):] == 0xAB).all()) and d_offs.cpu().tolist() == offs.tolist()
 
 def make_clip(rng, T, H, W, C):
     base = rng.integers(0, 256, (1, H, W, C))
@@ -29,7 +60,9 @@ def make_clip(rng, T, H, W, C):
     return np.clip(clip, 0, 255).astype(np.uint8)
 
 def one(rng):
-    W, H = int(rng.choice([7, 33, 64, 128, 256, 300])), int(rng.integers(1, 24))
+    W, H = int(rng.choice([7, 33, 64, 128, 256, 300, 1100])), int(rng.integers(1, 24))
+    if W == 1100:  # a row of more than 1024 units (RGB: more than 2048): the expansions' other ways to a unit's row
+        H = 1 + H % 6
     C = int(rng.choice([1, 1, 3])); T = int(rng.integers(20, 220))
     tm = int(rng.choice([O.DELTA_T, O.ABSOLUTE_T])); mm = int(rng.choice([O.COLLAPSE, O.COLLAPSE, O.COLLAPSE, O.NORMAL]))
     dtm = int(rng.choice([255, 7650, 7650, 1020])); crf = int(rng.choice([0, 3, 3, 6, 9]))
@@ -37,6 +70,11 @@ def one(rng):
         crf = 0
     depth = int(rng.choice([1, 3, 16, 64, 64]))
     cont = os.environ.get("FUZZ_CONTINUOUS") == "1" or (os.environ.get("FUZZ_CONTINUOUS") is None and rng.random() < 0.12)
+    form = str(rng.choice(["host", "device", "wire"]))
+    if cont and form == "wire":  # (Continuous events are stored as they are decoded: no wire form)
+        form = "device"
+    for key in ("form:" + form, "W:%d" % W):
+        STATS[key] = STATS.get(key, 0) + 1
     clip = make_clip(rng, T, H, W, C)
     ov = O.Video(W, H, C, time_mode=tm, multi_mode=mm, ref_time=255, delta_t_max=dtm)
     if cont:  # Mode::Continuous (the event-camera sources' mode, fed frames): the general arena step
@@ -52,7 +90,13 @@ def one(rng):
     k = 0
     while k < T:
         nb = min(int(rng.choice([1, 2, 17, 64, 65, 130])), T - k)
-        want = np.concatenate([ov.integrate_matrix(clip[k + i]) for i in range(nb)])
+        per = [ov.integrate_matrix(clip[k + i]) for i in range(nb)]
+        want = np.concatenate(per)
+        if form != "host":
+            if not device_batch(hv, clip[k:k + nb], per, C, form, len(want) > 2 and rng.random() < 0.15):
+                raise SystemExit(f"MISMATCH ({form}) W{W} H{H} C{C} T{T} tm{tm} mm{mm} dtm{dtm} crf{crf} depth{depth} at frame {k}+{nb}")
+            k += nb
+            continue
         if len(want) > 2 and rng.random() < 0.15:     # too small a buffer first: rollback, then the retry
             try:
                 hv.integrate_batch(clip[k:k + nb], out_cap=len(want) // 2)
