@@ -11,6 +11,12 @@ constexpr uint32_t kFramerStatusRing = 1u;       // an event reached past the fr
 constexpr uint32_t kFramerStatusMalformed = 2u;  // coordinates outside the plane / band
 constexpr uint32_t kFramerStatusRange = 4u;      // frame index out of range
 constexpr uint32_t kFramerRowsMaxFrames = 256;  // frames per adder_framer_tiles_kernel launch
+// launch geometry of the hand-out: past cap * units-per-block units a kernel takes further grid-stride passes
+constexpr uint32_t kFramerPopMaxBlocks = 2048;           // adder_framer_pop_kernel: blocks per frame at most
+constexpr uint32_t kFramerPopUnitsPerBlock = 1024;       // ... u8 units a block hands out per pass (4 per thread)
+constexpr uint32_t kFramerPopWideUnitsPerBlock = 256;    // ... u16 / u32 units a block hands out per pass
+constexpr uint32_t kFramerMinmaxMaxBlocks = 1024;        // adder_framer_minmax_kernel: blocks at most
+constexpr uint32_t kFramerMinmaxUnitsPerBlock = 4096;    // ... units that size its grid (16 per thread)
 
 struct FramerArgs {
     FramerPx *px;        // [n_units] {ts u64, last_filled i32, last_intensity u32}: one 16-byte record per unit

@@ -592,7 +592,7 @@ __global__ __launch_bounds__(256) void adder_framer_pop_kernel(const uint8_t *__
     if (value_type != 0u) {  // u16 / u32 elements: big-endian bytes (bincode fixint BE, driver.rs:279,395-398)
         const size_t base = (size_t)(f % ring_frames) * n_units;
         uint8_t *dst = out + ((size_t)blockIdx.y * n_units << value_type);
-        for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_units; i += gridDim.x * 256u) {
+        for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_units; i += gridDim.x * kFramerPopWideUnitsPerBlock) {
             const bool has = !masked || px[i].lastf >= (int32_t)f;
             if (value_type == 1u) {
                 const uint32_t v = has ? reinterpret_cast<const uint16_t *>(ring)[base + i] : 0u;
@@ -607,7 +607,7 @@ __global__ __launch_bounds__(256) void adder_framer_pop_kernel(const uint8_t *__
     }
     const uint8_t *src = ring + (size_t)(f % ring_frames) * n_units;
     uint8_t *dst = out + (size_t)blockIdx.y * n_units;
-    for (uint32_t i = (blockIdx.x * 256u + threadIdx.x) * 4u; i < n_units; i += gridDim.x * 1024u) {
+    for (uint32_t i = (blockIdx.x * 256u + threadIdx.x) * 4u; i < n_units; i += gridDim.x * kFramerPopUnitsPerBlock) {
         if (i + 4u <= n_units && !masked && ((n_units & 3u) == 0u)) {
             *reinterpret_cast<uint32_t *>(dst + i) = *reinterpret_cast<const uint32_t *>(src + i);
         } else {
@@ -671,17 +671,18 @@ extern "C" hipError_t adder_framer_launch_tiles(const void *ev, const uint64_t *
     return hipGetLastError();
 }
 extern "C" hipError_t adder_framer_launch_minmax(const FramerPx *px, uint32_t n, int32_t *out, hipStream_t s) {
-    const uint32_t grid = (n + 256u * 16u - 1u) / (256u * 16u);
-    hipLaunchKernelGGL(adder_framer_minmax_kernel, dim3(grid < 1024u ? (grid ? grid : 1u) : 1024u), dim3(256), 0, s, px,
-                       n, out);
+    const uint32_t grid = (n + kFramerMinmaxUnitsPerBlock - 1u) / kFramerMinmaxUnitsPerBlock;
+    hipLaunchKernelGGL(adder_framer_minmax_kernel,
+                       dim3(grid < kFramerMinmaxMaxBlocks ? (grid ? grid : 1u) : kFramerMinmaxMaxBlocks), dim3(256), 0, s,
+                       px, n, out);
     return hipGetLastError();
 }
 extern "C" hipError_t adder_framer_launch_pop(const uint8_t *ring, const FramerPx *px, uint32_t n_units,
                                               uint32_t ring_frames, int32_t f0, uint32_t nf, uint32_t masked,
                                               uint8_t *out, uint32_t value_type, hipStream_t s) {
     if (!nf) return hipSuccess;
-    uint32_t gx = (n_units + 1023u) / 1024u;
-    gx = gx > 2048u ? 2048u : gx;
+    uint32_t gx = (n_units + kFramerPopUnitsPerBlock - 1u) / kFramerPopUnitsPerBlock;
+    gx = gx > kFramerPopMaxBlocks ? kFramerPopMaxBlocks : gx;
     hipLaunchKernelGGL(adder_framer_pop_kernel, dim3(gx, nf), dim3(256), 0, s, ring, px, n_units, ring_frames, f0,
                        masked, out, value_type);
     return hipGetLastError();

@@ -9,6 +9,8 @@ import re
 import numpy as np
 import pytest
 
+import kernel_constants
+import quality_edge_cases as E
 import quality_oracle as Q
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,6 +97,87 @@ def test_bounds_hold_between_orders_on_a_larger_plane():
     assert abs(s - f) <= Q.ssim_bound(abs_sums, 1)
     pairwise = (float(np.sum(terms[0])) / (64.0 * n)) * 100.0
     assert abs(pairwise - f) <= Q.fsum_bound(abs_sums, 1, n)
+
+
+# ---- the edge tests' contents and shapes (tests/test_gpu_quality_edges.py) ---------------------------------
+
+@pytest.mark.parametrize("H,W", [(16, 16), (9, 17)])
+def test_fast_form_equals_the_literal_one_on_the_extremes(H, W):
+    """All 255, 255 against 0, checkerboard against its inverse, constant against noise: the integer-moment form's
+    largest sums and its negative windows."""
+    rng = np.random.default_rng(H * W)
+    for kind in range(len(E.EXTREMES)):
+        for Cn in (1, 3):
+            a, b = E.extreme_pair(kind, rng, H, W, Cn)
+            ls, lm, lsc = Q.literal_ssim(a, b)
+            fs, fm, fsc, _, _ = Q.fast_ssim(a, b)
+            assert (bits(lm) == bits(fm)).all(), (kind, Cn)
+            assert bits(lsc).tolist() == bits(fsc).tolist()
+            assert bits(ls) == bits(fs)
+            if kind == 0:
+                assert ls == 100.0
+            if kind == 2:  # every window holds 32 and 32: one value, the most negative there is
+                m2, cv = 2.0 * 127.5 * 127.5, 64.0 * 127.5 * 127.5  # means 127.5; variances 64 * 127.5^2, covariance minus that
+                want = ((m2 + Q.C1) * (2.0 * -cv + Q.C2)) / ((m2 + Q.C1) * (cv + cv + Q.C2))
+                assert (bits(fm) == bits(want)).all() and want < -0.9999
+                if (H, W) == (16, 16):  # (the frame's figure is a sequential sum: its last digits follow the window count)
+                    assert ls == fs == -99.99437515819864
+    a, b = E.extreme_pair(1, rng, H, W, 1)
+    assert Q.mse_psnr(a, b)[0] == 65025.0
+
+
+def test_unlike_channels_are_unlike():
+    rng = np.random.default_rng(8)
+    a, b = E.unlike_channels(rng, 3, 12, 10, 3)
+    for f in range(3):
+        roles = [(f + ch) % 3 for ch in range(3)]
+        assert np.array_equal(a[f, ..., roles.index(0)], b[f, ..., roles.index(0)])
+        assert np.array_equal(255 - a[f, ..., roles.index(1)], b[f, ..., roles.index(1)])
+        scores = Q.fast_ssim(a[f], b[f])[2]
+        assert scores[roles.index(0)] == 1.0 and scores[roles.index(1)] < -0.5 < scores[roles.index(2)] < 0.5
+    a, b = E.unlike_channels(rng, 2, 12, 10, 1)
+    assert np.abs(a[0].astype(int) - b[0]).max() <= 3 and np.abs(a[1].astype(int) - b[1]).max() > 100
+
+
+def test_edge_shapes_straddle_the_kernel_constants():
+    k = kernel_constants.quality()
+    assert k["kSsimTileW"] == k["kQualBlock"] - 8 and k["kSsimTileH"] % 8 == 0
+    tw, th = k["kSsimTileW"], k["kSsimTileH"]
+    ww = [w - 7 for w in E.tile_edge_widths(k)]
+    wh = [h - 7 for h in E.tile_edge_heights(k)]
+    assert min(ww) == 1 and min(wh) == 1
+    assert {tw - 1, tw, tw + 1, 2 * tw, 2 * tw + 1} <= set(ww)           # a tile less one, full, and one column over
+    assert {w % tw for w in ww if w > tw} >= {1, 7, 8, 0}                # last tiles of 1, 7 and 8 windows, and full
+    assert {th - 1, th, th + 1, 2 * th, 2 * th + 1} <= set(wh)
+    assert {min(th, h) % 8 for h in wh} == set(range(8))                 # every exit phase of the unrolled row loop
+    assert any(h > th and h % th == 1 for h in wh)                       # a tile of a single window row below a full one
+    # at today's constants these are the lists the tests were written for
+    if (tw, th) == (248, 32):
+        assert [w + 7 for w in ww] == [8, 9, 15, 254, 255, 256, 262, 263, 503, 504]
+        assert set(h + 7 for h in wh) >= {8, 14, 15, 16, 38, 39, 40, 71, 72}
+    W, H, clamp = E.sse_clamp_plane(k)
+    assert clamp == k["kSseMaxBlocks"] * k["kSseBytesPerBlock"] and clamp < W * H <= clamp + W and (W * H) % 16 == 0
+    assert W < 65536 and H < 65536
+
+
+def test_known_changes_have_the_stated_sum():
+    rng = np.random.default_rng(12)
+    a = rng.integers(0, 256, 300000, dtype=np.uint8)
+    b, sse = E.known_changes(rng, a, 200000)
+    d = a.astype(np.int64) - b.astype(np.int64)
+    assert int((d * d).sum()) == sse and 900 < np.count_nonzero(d) < 1100
+    assert d[0] and d[-1] and d[199999] and d[200000] and d[15] and d[16]
+
+
+def test_kernel_constants_fail_loudly():
+    text = "constexpr uint32_t kA = 256;\nconstexpr uint32_t kB = kA * 16u * 8u;  // c\nconstexpr uint32_t kC = kA - 8;\n"
+    assert kernel_constants.parse_u32_constants(text, ("kA", "kB", "kC")) == {"kA": 256, "kB": 32768, "kC": 248}
+    with pytest.raises(KeyError):
+        kernel_constants.parse_u32_constants(text, ("kA", "kMissing"))
+    with pytest.raises(KeyError):
+        kernel_constants.parse_u32_constants("constexpr uint32_t kD = sizeof(int);", ("kD",))
+    f = kernel_constants.framer()
+    assert all(v > 0 for v in f.values()) and len(f) == 5
 
 
 # ---- the library ------------------------------------------------------------------------------------------------
