@@ -18,6 +18,8 @@ TIME_DELTA_T, TIME_ABSOLUTE_T, TIME_MIXED = 0, 1, 2
 MULTI_NORMAL, MULTI_COLLAPSE = 0, 1
 CONTENT_STATIC, CONTENT_NOISE, CONTENT_SCENE = 0, 1, 2
 D_MAX, D_ZERO_INTEGRATION, D_EMPTY, C_NONE = 127, 128, 255, 0xFF
+VIEW_INTENSITY, VIEW_D, VIEW_DELTA_T, VIEW_SAE = 0, 1, 2, 3   # FramedViewMode (include/adder_framer.h ADDER_VIEW_*)
+SHOW_FEATURES_OFF, SHOW_FEATURES_INSTANT, SHOW_FEATURES_HOLD = 0, 1, 2   # ShowFeatureMode (include/adder_hip.h)
 
 # adder_hip_last_batch_kernel (include/adder_hip.h)
 (KERNEL_LEAN, KERNEL_GENERIC, KERNEL_CONTINUOUS, KERNEL_BOUNDED, KERNEL_CONSTANT_RUNS, KERNEL_RUN_RECORDS,
@@ -165,6 +167,10 @@ SYMBOLS = {
     "adder_hip_running_intensities": (_i32, [_vp, _vp]),
     "adder_hip_enable_running_intensities": (_i32, [_vp, _i32]),
     "adder_hip_running_intensities_device": (_i32, [_vp, _vp, _vp]),
+    "adder_hip_set_view_mode": (_i32, [_vp, _u32, _f32]),
+    "adder_hip_set_show_features": (_i32, [_vp, _u32]),
+    "adder_hip_display_frame": (_i32, [_vp, _vp]),
+    "adder_hip_display_frame_device": (_i32, [_vp, _vp, _vp]),
     "adder_hip_last_batch_ms": (_f32, [_vp]),
     "adder_hip_launch_plan_settled": (_i32, [_vp]),
     "adder_hip_last_batch_kernel": (_u32, [_vp]),

@@ -28,6 +28,14 @@ def crf_feature_radius(crf, width, height):
     return int(np.float32(CRF_FEATURE_RADIUS[crf]) * np.float32(min(width, height)))
 
 
+def practical_d_max_exact(delta_t_max, ref_time):
+    """The D view's divisor, log2(255 * (delta_t_max / ref_time)) with the reference's integer division and f32 product
+    (video.rs), the logarithm exact and rounded to f32 -- what the context uses unless the caller pins another value."""
+    import math
+    arg = np.float32(255.0) * np.float32(int(delta_t_max) // int(ref_time))
+    return float(np.float32(math.log2(float(arg)))) if arg > 0 else float("-inf")
+
+
 class HipVideo:
     def __init__(self, width, height, channels=1, *, row_begin=0, row_end=None,
                  time_mode=N.TIME_ABSOLUTE_T, multi_mode=N.MULTI_COLLAPSE, ref_time=255,
@@ -155,6 +163,30 @@ class HipVideo:
         assert d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= self.n_units
         N.check(self.h, self.L.adder_hip_running_intensities_device(self.h, d_out.data_ptr(),
                                                                      C.c_void_p(stream) if stream else None))
+        return d_out
+
+    # ---- the live view: what the plane shows, and the plane with the features drawn in ----------
+    def set_view_mode(self, view, practical_d_max=None):
+        """Video::instantaneous_view_mode (video.rs:331): N.VIEW_INTENSITY / VIEW_D / VIEW_DELTA_T / VIEW_SAE, from the next
+        integrated frame on.  practical_d_max (D view): None = practical_d_max_exact of the context's current delta_t_max,
+        followed when that changes; a number pins it (the reference's fast_math::log2_raw value, or Prophesee's 32.0)."""
+        N.check(self.h, self.L.adder_hip_set_view_mode(self.h, int(view), 0.0 if practical_d_max is None else float(practical_d_max)))
+
+    def set_show_features(self, mode):
+        """ShowFeatureMode (utils/viz.rs:76-86): N.SHOW_FEATURES_OFF / _INSTANT / _HOLD."""
+        N.check(self.h, self.L.adder_hip_set_show_features(self.h, int(mode)))
+
+    def display_frame(self):
+        """Video::display_frame_features after the last integrated frame, [rows, width, channels] u8."""
+        out = np.zeros(self.n_units, np.uint8)
+        N.check(self.h, self.L.adder_hip_display_frame(self.h, out.ctypes.data))
+        return out.reshape(self.rows, self.width, self.channels)
+
+    def display_frame_device(self, d_out, stream=None):
+        """The same into the uint8 CUDA tensor d_out (n_units bytes at any byte address), queued on `stream` behind every
+        batch of this context, without a host synchronisation (adder_hip_display_frame_device)."""
+        assert d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= self.n_units
+        N.check(self.h, self.L.adder_hip_display_frame_device(self.h, d_out.data_ptr(), C.c_void_p(stream) if stream else None))
         return d_out
 
     # ---- host-buffer entry points --------------------------------------------------------

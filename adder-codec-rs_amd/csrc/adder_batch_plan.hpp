@@ -27,6 +27,10 @@ struct BatchPlanIn {
     float cr_time;
     uint64_t frames_done, run_bound;
     uint8_t records_only, wire_batch;           // the batch hands its records out / writes the raw sink's records
+    // what the running-intensities side plane shows while it is on (ADDER_VIEW_*); 0 with the plane off and in the
+    // Intensity view.  D, DeltaT and SAE need the root's best event in full and last_fired_t in both time modes: only the
+    // generic and the Continuous frame kernels have a view instantiation (kVarView) -- no other kernel may be chosen
+    uint8_t side_view;
     // the batch
     uint32_t num_frames;
     float time_spanned;
@@ -50,7 +54,7 @@ struct BatchPlan {
 // describe), so the choice is sticky until adder_hip_reset: update_quality_manual can lower delta_t_max mid-stream
 // (video.rs:1264-1287).
 inline bool lean_possible(const BatchPlanIn &in) {
-    return !in.generic_sticky && !in.perpx && !in.needs_perpx && in.multi_mode == ADDER_MULTI_COLLAPSE &&
+    return !in.generic_sticky && !in.perpx && !in.needs_perpx && !in.side_view && in.multi_mode == ADDER_MULTI_COLLAPSE &&
            (float)in.delta_t_max <= in.time_spanned;
 }
 
@@ -68,7 +72,7 @@ inline size_t worst_case_events_per_frame(const BatchPlanIn &in) {
 // (adder_pixel.hpp kRrFlushPop).
 inline bool rr_possible(const BatchPlanIn &in, bool frac_time_seen, bool pop_at_once_ok) {
     const float T = in.time_spanned;
-    if (in.continuous || in.perpx || in.needs_perpx || frac_time_seen) return false;
+    if (in.continuous || in.perpx || in.needs_perpx || in.side_view || frac_time_seen) return false;
     const double dtm = (double)(in.delta_t_max > in.dtm_max_seen ? in.delta_t_max : in.dtm_max_seen);
     if (!((float)in.delta_t_max > T) && !pop_at_once_ok) return false;
     if (!(T >= 1.0f) || T != (float)(uint32_t)T || T > 65536.0f) return false;
@@ -119,7 +123,7 @@ inline BatchPlan plan_batch(const BatchPlanIn &in) {
                 (abs_t ? kVarAbsT : 0u) | (generic ? kVarGeneric : 0u) | (in.continuous ? kVarContinuous : 0u) |
                 (in.n_units >= 4u ? kVarWide : 0u) | (cb ? kVarBounded : 0u) | (cr ? kVarConstRuns : 0u) |
                 (lr ? kVarLeanRuns : 0u) | (rr ? kVarRunRecords : 0u) | (in.wire_batch ? kVarWire : 0u) |
-                ((in.records_only && !lr) ? kVarLeanLog : 0u);
+                ((in.records_only && !lr) ? kVarLeanLog : 0u) | (in.side_view ? kVarView : 0u);
     // per-event records go to a log per segment and chunk, sized by the hard bound of what a segment can emit (pop_top and
     // a flush exclude each other in one frame when delta_t_max >= 2 * time: 2 instead of 3 per frame); lean records are
     // 12 bytes in AbsoluteT, 8 otherwise (adder_pixel.hpp lean_decode8)

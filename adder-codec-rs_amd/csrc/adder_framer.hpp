@@ -11,7 +11,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "adder_pixel.hpp"  // ADDER_HD, frame_value_u8
+#include "adder_pixel.hpp"  // ADDER_HD, view_value_u8, kView*
 
 namespace adder {
 
@@ -48,7 +48,6 @@ struct FramerConsts {
     uint32_t delta_t_max;    // DeltaT / SAE views
     uint32_t value_type;     // the frame element type T of FrameSequence<T>: 0 u8, 1 u16, 2 u32 (scale_intensity.rs:54-209)
 };
-constexpr uint32_t kViewIntensity = 0, kViewD = 1, kViewDeltaT = 2, kViewSae = 3;
 
 ADDER_HD FramerConsts framer_consts(uint32_t tpf, uint32_t ref_interval, uint32_t abs_t, uint32_t round_up,
                                     uint32_t view_mode = 0, uint32_t source_type = 0, float practical_d_max = 0.0f,
@@ -72,12 +71,12 @@ ADDER_HD FramerConsts framer_consts(uint32_t tpf, uint32_t ref_interval, uint32_
 // as the framer hands it over (AbsoluteT streams: minus the pixel's previous clock, except in the SAE view, :1022-1028),
 // clock / prev_clock = the pixel's running timestamp after / before the event, as u32 (`as DeltaT`).
 ADDER_HD uint32_t framer_value_u8(uint32_t d, uint32_t te, uint32_t clock, uint32_t prev_clock, const FramerConsts &k) {
-    if (k.view_mode == kViewD) return f32_as_u8((float)d / k.practical_d_max * 255.0f);
-    if (k.view_mode == kViewDeltaT) return f32_as_u8((float)te / (float)k.delta_t_max * 255.0f);
-    if (k.view_mode == kViewSae) return f32_as_u8((float)(clock - prev_clock) / (float)k.delta_t_max * 255.0f);
+    // (the D, DeltaT and SAE arms and the U8 source's Intensity arm: adder_pixel.hpp view_value_u8, shared with the
+    // transcoder's running_intensities)
+    if (k.view_mode != kViewIntensity || k.source_type == 0u)
+        return view_value_u8(d, te, clock, prev_clock, ViewConsts{k.view_mode, k.ref_interval, k.delta_t_max, k.practical_d_max});
     const double intensity = event_intensity_f64(d, te);
     const double tpf = (double)k.ref_interval;
-    if (k.source_type == 0u) return f64_as_u8(intensity * tpf);
     const double full = k.source_type == 1u ? 65535.0 : k.source_type == 2u ? 4294967295.0 : 18446744073709551616.0;
     return f64_as_u8(intensity / full * tpf * 255.0);
 }

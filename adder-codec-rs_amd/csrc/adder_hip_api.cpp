@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <map>
 #include <new>
@@ -81,6 +82,13 @@ struct AdderHipCtx {
     uint8_t *fset = nullptr;         // [rows][width] VideoState::features membership
     uint32_t *d_feat_counters = nullptr;
     uint32_t last_new_features = 0;
+    // the live view (Video::instantaneous_view_mode, video.rs:331; display_frame_features, :328)
+    uint32_t view_mode = 0;          // ADDER_VIEW_*: what the running-intensities plane shows
+    float practical_d_max = 0.0f;    // D view: the caller's value; <= 0: exact log2 of 255 * (delta_t_max / ref_time)
+    uint32_t show_features = 0;      // ShowFeatureMode: 0 Off, 1 Instant, 2 Hold
+    uint8_t *d_display = nullptr;    // staging of adder_hip_display_frame
+    size_t d_display_cap = 0;
+    uint32_t *fstamp = nullptr;      // [rows][width] frame (frames_done + 1 of its batch) in which the pixel last became a feature
     bool perpx = false;              // sticky until adder_hip_reset / reset_c_thresh
     // c_thresh / c_increase_counter: identical in every pixel (adder_pixel.hpp header comment)
     uint8_t c_thresh = 10, c_counter = 1;
@@ -324,7 +332,7 @@ static void free_ctx(AdderHipCtx *c) {
                     c->dv_bdt,  c->dv_bd,   c->running_base, c->d_new_xy, c->cn_integ, c->cn_dt, c->cn_bdt, c->cn_meta,
                     c->snap.cn_integ, c->snap.cn_dt, c->snap.cn_bdt, c->snap.cn_meta,
                     c->d_offsets, c->d_frames, c->d_events, c->d_chunks, c->d_wire,
-                    c->cth_px, c->cctr_px, c->fset, c->d_feat_counters, c->snap.cth_px, c->snap.cctr_px, c->snap.fset,
+                    c->cth_px, c->cctr_px, c->fset, c->fstamp, c->d_display, c->d_feat_counters, c->snap.cth_px, c->snap.cctr_px, c->snap.fset,
                     c->snap.running};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -430,6 +438,20 @@ static StepConsts make_consts(const AdderHipCtx *c, float time_spanned) {
     return sc;
 }
 
+// D view's divisor when the caller has not pinned one: the reference's argument (an integer division, video.rs) with
+// the logarithm taken exactly (its fast_math::log2_raw is an approximation: include/adder_framer.h)
+static float practical_d_max_exact(uint32_t delta_t_max, uint32_t ref_time) {
+    return (float)std::log2((double)(255.0f * (float)(delta_t_max / ref_time)));
+}
+static ViewConsts make_view(const AdderHipCtx *c) {
+    ViewConsts v;
+    v.view_mode = c->view_mode;
+    v.ref_time = c->p.ref_time;
+    v.delta_t_max = c->p.delta_t_max;
+    v.practical_d_max = c->practical_d_max > 0.0f ? c->practical_d_max : practical_d_max_exact(c->p.delta_t_max, c->p.ref_time);
+    return v;
+}
+
 static void base_args(const AdderHipCtx *c, FrameArgs *a) {
     memset(a, 0, sizeof *a);
     a->hdr = c->hdr;
@@ -508,6 +530,7 @@ static int init_state(AdderHipCtx *c) {
     c->perpx = false;
     c->sparse_mode = false;
     if (c->fset) HIPCHK(c, hipMemsetAsync(c->fset, 0, (size_t)c->rows * p.width, c->stream));
+    if (c->fstamp) HIPCHK(c, hipMemsetAsync(c->fstamp, 0, (size_t)c->rows * p.width * sizeof(uint32_t), c->stream));
     c->running_t = 0.0f;
     c->frames_done = 0;
     c->poisoned = false;
@@ -825,6 +848,10 @@ static int prepare_feature_set(AdderHipCtx *c, hipStream_t s) {
         HIPCHK(c, dalloc(&c->fset, (size_t)c->rows * c->p.width));
         HIPCHK(c, hipMemsetAsync(c->fset, 0, (size_t)c->rows * c->p.width, s));
     }
+    if (!c->fstamp && !is_band(c)) {
+        HIPCHK(c, dalloc(&c->fstamp, (size_t)c->rows * c->p.width));
+        HIPCHK(c, hipMemsetAsync(c->fstamp, 0, (size_t)c->rows * c->p.width * sizeof(uint32_t), s));
+    }
     if (!c->d_feat_counters) HIPCHK(c, dalloc(&c->d_feat_counters, 4));
     HIPCHK(c, hipMemsetAsync(c->d_feat_counters, 0, 4 * sizeof(uint32_t), s));
     return ADDER_OK;
@@ -938,6 +965,7 @@ static BatchPlanIn plan_input(const AdderHipCtx *c, uint32_t num_frames, float t
     in.cr_valid = c->cr_valid; in.frac_time_seen = c->frac_time_seen; in.cr_time = c->cr_time;
     in.frames_done = c->frames_done; in.run_bound = c->run_bound;
     in.records_only = c->records_only; in.wire_batch = c->wire_batch;
+    in.side_view = c->running_enabled ? (uint8_t)c->view_mode : 0u;
     in.num_frames = num_frames; in.time_spanned = time_spanned;
     return in;
 }
@@ -1067,6 +1095,8 @@ static FeatureArgs feature_args(const AdderHipCtx *c) {
     fa.plane_h = c->p.height;
     fa.new_xy = nullptr;
     fa.new_cap = 0;
+    fa.stamp = c->fstamp;
+    fa.stamp_base = (uint32_t)(c->frames_done + 1u);  // (enqueue_frames advances frames_done behind the launches)
     return fa;
 }
 
@@ -1485,6 +1515,7 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
         b.snap_dv_bd = sd ? c->snap.dv_bd : nullptr;
     }
     b.run_max = (lr || rr) ? c->d_run_max : nullptr;
+    b.view = make_view(c);
     b.wofs_ring = c->wofs_ring;
     b.wcur = c->wcur;
     static_assert((1u << kParkGroupShift) % kExpandSegs == 0, "a group of segments must hold whole expansion waves");
@@ -2750,6 +2781,8 @@ static SparseArgs sparse_args(AdderHipCtx *c) {
     a.row_begin = c->p.row_begin;
     a.rows = c->rows;
     a.sc = make_consts(c, 0.0f);
+    a.view = make_view(c);
+    if (!a.running) a.view.view_mode = kViewIntensity;
     return a;
 }
 
@@ -2876,6 +2909,77 @@ extern "C" int adder_hip_running_intensities_device(AdderHipCtx *c, uint8_t *d_d
     HIPCHK(c, hipMemcpyAsync(d_dst, c->running, c->n_units, hipMemcpyDeviceToDevice, s));
     HIPCHK(c, hipEventRecord(c->ri_copy_e, s));
     c->ri_copy_pending = true;
+    return ADDER_OK;
+}
+
+// ---- the live view (include/adder_hip.h): what the plane shows, and the plane with the features drawn in ----
+extern "C" int adder_hip_set_view_mode(AdderHipCtx *c, uint32_t view_mode, float practical_d_max) {
+    if (!c) return ADDER_E_BAD_PARAMS;
+    if (view_mode > kViewSae) return fail(c, ADDER_E_BAD_PARAMS, "bad view mode %u (ADDER_VIEW_*: 0 .. 3)", view_mode);
+    if (practical_d_max != practical_d_max) return fail(c, ADDER_E_BAD_PARAMS, "practical_d_max is NaN");
+    if (c->pending || c->f_submitted != c->f_collected) return fail(c, ADDER_E_BAD_PARAMS, "work is in flight on this context");
+    c->view_mode = view_mode;
+    c->practical_d_max = practical_d_max > 0.0f ? practical_d_max : 0.0f;
+    return ADDER_OK;
+}
+
+extern "C" int adder_hip_set_show_features(AdderHipCtx *c, uint32_t mode) {
+    if (!c) return ADDER_E_BAD_PARAMS;
+    if (mode > 2u) return fail(c, ADDER_E_BAD_PARAMS, "bad ShowFeatureMode %u (0 Off, 1 Instant, 2 Hold)", mode);
+    if (mode != 0u && is_band(c))
+        return fail(c, ADDER_E_BAD_PARAMS, "a row band cannot show features: a cross reaches two rows into the neighbouring band");
+    c->show_features = mode;
+    return ADDER_OK;
+}
+
+// the display frame into device memory on stream s, behind everything the context has queued (no host synchronisation)
+static int display_frame_queue(AdderHipCtx *c, uint8_t *d_dst, hipStream_t s) {
+    if (is_band(c))
+        return fail(c, ADDER_E_BAD_PARAMS, "a row band has no display frame: a cross reaches two rows into the neighbouring band");
+    if (!c->running) return fail(c, ADDER_E_BAD_PARAMS, "the running-intensities plane was never enabled before a batch");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->ri_copy_e) HIPCHK(c, hipEventCreateWithFlags(&c->ri_copy_e, hipEventDisableTiming));
+    if (!c->ri_src_e) HIPCHK(c, hipEventCreateWithFlags(&c->ri_src_e, hipEventDisableTiming));
+    if (s != c->stream) {  // (adder_hip_running_intensities_device: host-pointer batches and resets queue on the context's stream)
+        HIPCHK(c, hipEventRecord(c->ri_src_e, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(s, c->ri_src_e, 0));
+    }
+    if (c->pending_stream && c->pending_stream != c->stream && c->pending_stream != s) {
+        HIPCHK(c, hipEventRecord(c->ri_src_e, c->pending_stream));
+        HIPCHK(c, hipStreamWaitEvent(s, c->ri_src_e, 0));
+    }
+    // video.rs:742-744, 883-887: a clone of the plane; crosses only with feature detection on, and only once a frame
+    // has been integrated in feature mode (the membership plane exists; frame stamps start at 1)
+    const bool crosses = c->show_features != 0u && c->feat_detect && c->fset && c->fstamp && c->frames_done != 0;
+    if (crosses)
+        HIPCHK(c, adder_launch_display(c->running, c->fset, c->show_features == 1u ? c->fstamp : nullptr, (uint32_t)c->frames_done,
+                                       c->p.width, c->rows, c->p.channels, d_dst, s));
+    else
+        HIPCHK(c, hipMemcpyAsync(d_dst, c->running, c->n_units, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipEventRecord(c->ri_copy_e, s));
+    c->ri_copy_pending = true;
+    return ADDER_OK;
+}
+
+extern "C" int adder_hip_display_frame_device(AdderHipCtx *c, uint8_t *d_dst, void *stream) {
+    if (!c) return ADDER_E_BAD_PARAMS;
+    if (!d_dst) return fail(c, ADDER_E_BAD_PARAMS, "display frame: null destination");
+    return display_frame_queue(c, d_dst, (hipStream_t)stream);
+}
+
+extern "C" int adder_hip_display_frame(AdderHipCtx *c, uint8_t *dst) {
+    if (!c) return ADDER_E_BAD_PARAMS;
+    if (!dst) return fail(c, ADDER_E_BAD_PARAMS, "display frame: null destination");
+    if (is_band(c) || !c->running) return display_frame_queue(c, nullptr, nullptr);  // (its refusals)
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc_ = settle_reset(c); if (rc_ != ADDER_OK) return rc_; }
+    void *vp = c->d_display;
+    { int rc_ = ensure(c, &vp, &c->d_display_cap, c->n_units); if (rc_ != ADDER_OK) return rc_; }
+    c->d_display = (uint8_t *)vp;
+    int rc = display_frame_queue(c, c->d_display, c->stream);
+    if (rc != ADDER_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(dst, c->d_display, c->n_units, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return ADDER_OK;
 }
 

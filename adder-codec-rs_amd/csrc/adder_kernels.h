@@ -161,6 +161,8 @@ struct BatchArgs {
     // the integer-state kernels (lean runs, run records) report the longest run -- frames a root has accumulated -- their units
     // hold at the end of a launch: the host's bound on "rho * 255 and rho * time_spanned stay exact in binary32" (may be null)
     uint32_t *run_max;
+    // what the side plane shows when the batch's variant has kVarView (Video::instantaneous_view_mode: D, DeltaT, SAE)
+    ViewConsts view;
 };
 constexpr uint32_t kRunReportMin = 16384;  // runs shorter than this are not reported (BatchResult::max_run 0 = "below it")
 constexpr uint32_t kTimelineChunks = 64;
@@ -233,6 +235,7 @@ struct SparseArgs {
     uint32_t c_max, c_vel, max_nodes, stage_events;
     uint32_t width, channels, row_begin, rows;
     StepConsts sc;              // (time_spanned, running_t, cth are set per step)
+    ViewConsts view;            // what the side plane shows (view_mode != 0: the kernel's view instantiation)
 };
 
 // handle_features / handle_roi of one context (video.rs:865-1112)
@@ -250,6 +253,9 @@ struct FeatureArgs {
     uint32_t plane_h;     // PlaneSize height
     uint32_t *new_xy;     // list of this frame's new features, or nullptr
     uint32_t new_cap;     // its capacity; counters[1] counts the entries
+    // ShowFeatureMode::Instant: [rows][width], the stamp of the frame in which the pixel last became a feature (0: never)
+    uint32_t *stamp;      // or nullptr
+    uint32_t stamp_base;  // frame f of the batch stamps stamp_base + f
 };
 constexpr uint32_t kFeatureHalo = 3;  // rows the FAST 9_16 ring reaches over (adder_pixel.hpp kFastBorder)
 
@@ -336,6 +342,10 @@ hipError_t adder_launch_features(const adder::BatchArgs *b, uint32_t f, const ad
 // the c_thresh resets around features found by OTHER row bands (x | plane y << 16), clipped to this band's rows
 hipError_t adder_launch_feature_apply(const adder::BatchArgs *b, const adder::FeatureArgs *fa, const uint32_t *xy, uint32_t n,
                                       hipStream_t stream);
+// Video::display_frame_features (adder_display.hip): dst[rows][width][channels] = the running plane with a white cross
+// on every pixel p of [rows][width] with (stamp ? stamp[p] == stamp_val : member[p] != 0); member == stamp == null: a copy
+hipError_t adder_launch_display(const uint8_t *running, const uint8_t *member, const uint32_t *stamp, uint32_t stamp_val,
+                                uint32_t width, uint32_t rows, uint32_t channels, uint8_t *dst, hipStream_t stream);
 hipError_t adder_launch_synth(uint8_t *dst, int content, uint64_t seed, uint32_t W, uint32_t H, uint32_t C,
                               uint32_t y0, uint32_t rows, uint32_t k0, uint32_t nframes, hipStream_t stream);
 }

@@ -532,12 +532,13 @@ __device__ __forceinline__ void lean_frames(const BatchArgs *__restrict__ b, con
         store_vec<NTS>(a.dt0, u0, dv);
         store_vec<NTS>(a.bdt0, u0, bv);
         if (ABS_T) store_vec<NTS>(a.lastf, u0, lfv);
+        // (Intensity view: the plan sends the other views to adder_frame_kernel / adder_cont_kernel, adder_batch_plan.hpp)
         if (a.running) {  // side plane (the host keeps nb == 1 while it is enabled)
 #pragma unroll
             for (uint32_t j = 0; j < N; ++j)
                 if (L::lane(active[j] & px[j].has0))
-                    a.running[u0 + j] = (uint8_t)frame_value_u8(lean_bd_from_thr(f32_to_bits(px[j].thr)),
-                                                                f32_as_u32(px[j].bdt), (double)sc.ref_time);
+                    a.running[u0 + j] = (uint8_t)view_value_u8(lean_bd_from_thr(f32_to_bits(px[j].thr)),
+                                                                f32_as_u32(px[j].bdt), 0u, 0u, view_intensity(sc.ref_time));
         }
     }
 }
@@ -1017,8 +1018,8 @@ __device__ __forceinline__ void wide_step_pair(const BatchArgs *__restrict__ b, 
 #pragma unroll
         for (uint32_t j = 0; j < N; ++j)
             if (L::lane(active[j] & px[j].has0))
-                a.running[u0 + j] = (uint8_t)frame_value_u8(lean_bd_from_thr(f32_to_bits(px[j].thr)),
-                                                            f32_as_u32(px[j].bdt), (double)sc.ref_time);
+                a.running[u0 + j] = (uint8_t)view_value_u8(lean_bd_from_thr(f32_to_bits(px[j].thr)),
+                                                            f32_as_u32(px[j].bdt), 0u, 0u, view_intensity(sc.ref_time));
     }
 }
 
@@ -1140,7 +1141,10 @@ struct SegLog {
     }
 };
 
-template <bool COLLAPSE, bool ABS_T>
+// VIEW: the side plane shows D, DeltaT or SAE (BatchArgs::view; kVarView).  last_fired_t then lives in its plane in
+// DeltaT too -- the Collapse branch of a popped arena sets it in both time modes (event_pixel_tree.rs:257) and the SAE
+// view reads it.  The other instantiations are the code they were.
+template <bool COLLAPSE, bool ABS_T, bool VIEW>
 __device__ __forceinline__ void gen_run_segment(const BatchArgs *__restrict__ b, const FrameArgs &a, uint32_t nb,
                                                 uint32_t u0, uint32_t gw, uint32_t lane, uint4 *lds_levels) {
     constexpr uint32_t N = kUnitsPerLane;
@@ -1155,9 +1159,9 @@ __device__ __forceinline__ void gen_run_segment(const BatchArgs *__restrict__ b,
         load_vec(a.integ0, u0, iv);
         load_vec(a.dt0, u0, dv);
         load_vec(a.bdt0, u0, bv);
-        if (ABS_T) load_vec(a.lastf, u0, lfv);
+        if (ABS_T || VIEW) load_vec(a.lastf, u0, lfv);
 #pragma unroll
-        for (uint32_t j = 0; j < N; ++j) px[j] = px_unpack(hdrv[j], iv[j], dv[j], bv[j], ABS_T ? lfv[j] : 0.0f);
+        for (uint32_t j = 0; j < N; ++j) px[j] = px_unpack(hdrv[j], iv[j], dv[j], bv[j], (ABS_T || VIEW) ? lfv[j] : 0.0f);
     }
     StepConsts sc = a.sc;
     // c_thresh / c_increase_counter per unit once feature-driven rate control or an ROI has made them differ
@@ -1283,7 +1287,7 @@ __device__ __forceinline__ void gen_run_segment(const BatchArgs *__restrict__ b,
         store_vec(a.integ0, u0, iv);
         store_vec(a.dt0, u0, dv);
         store_vec(a.bdt0, u0, bv);
-        if (ABS_T) store_vec(a.lastf, u0, lfv);
+        if (ABS_T || VIEW) store_vec(a.lastf, u0, lfv);
         if (perpx) {
 #pragma unroll
             for (uint32_t j = 0; j < N; ++j) {
@@ -1292,16 +1296,19 @@ __device__ __forceinline__ void gen_run_segment(const BatchArgs *__restrict__ b,
             }
         }
         if (a.running) {  // side plane (the host keeps nb == 1 while it is enabled)
+            const ViewConsts vc = VIEW ? b->view : view_intensity(sc.ref_time);
+            // running_t after this frame's integrate (`self.running_t += time`, event_pixel_tree.rs:336)
+            const uint32_t clock = VIEW ? f32_as_u32(fadd(sc.running_t, sc.time_spanned)) : 0u;
 #pragma unroll
             for (uint32_t j = 0; j < N; ++j)
                 if (u0 + j < a.n_units && px[j].m != 0u)
-                    a.running[u0 + j] = (uint8_t)frame_value_u8(px[j].n0.bd, f32_as_u32(px[j].n0.bdt),
-                                                                (double)sc.ref_time);
+                    a.running[u0 + j] = (uint8_t)view_value_u8(px[j].n0.bd, f32_as_u32(px[j].n0.bdt), clock,
+                                                               VIEW ? f32_as_u32(px[j].lastf) : 0u, vc);
         }
     }
 }
 
-template <bool COLLAPSE, bool ABS_T>
+template <bool COLLAPSE, bool ABS_T, bool VIEW = false>
 __global__ __launch_bounds__(kBlockThreads, 4) void adder_frame_kernel(const BatchArgs *__restrict__ b, uint32_t f,
                                                                       uint32_t nb) {
     __shared__ __attribute__((aligned(16))) uint4 s_levels[kWavesPerBlock][kGenLdsLevels * kWaveUnits];
@@ -1311,7 +1318,7 @@ __global__ __launch_bounds__(kBlockThreads, 4) void adder_frame_kernel(const Bat
     // (a capped grid walks the segments, like the lean kernel; the wave's LDS slice is its own, no barrier needed)
     for (uint32_t gw = blockIdx.x * kWavesPerBlock + tid / kWave; gw < a.num_waves; gw += gridDim.x * kWavesPerBlock) {
         const uint32_t u0 = gw * kWaveUnits + lane * kUnitsPerLane;
-        gen_run_segment<COLLAPSE, ABS_T>(b, a, nb, u0, gw, lane, s_levels[tid / kWave]);
+        gen_run_segment<COLLAPSE, ABS_T, VIEW>(b, a, nb, u0, gw, lane, s_levels[tid / kWave]);
     }
 }
 
@@ -1697,8 +1704,8 @@ __device__ __forceinline__ void cb_run_segment(const BatchArgs *__restrict__ b, 
 #pragma unroll
             for (uint32_t j = 0; j < N; ++j)
                 if (u0 + j < n_units_u && px[j].m != 0u)
-                    a.running[u0 + j] = (uint8_t)frame_value_u8(lean_bd_from_thr(f32_to_bits(px[j].thr0)),
-                                                                f32_as_u32(px[j].bdt0), (double)sc.ref_time);
+                    a.running[u0 + j] = (uint8_t)view_value_u8(lean_bd_from_thr(f32_to_bits(px[j].thr0)),
+                                                                f32_as_u32(px[j].bdt0), 0u, 0u, view_intensity(sc.ref_time));
         }
     }
 #ifdef ADDER_CB_PROFILE
@@ -1903,8 +1910,8 @@ __device__ __forceinline__ void cr_run_segment(const BatchArgs *__restrict__ b, 
 #pragma unroll
             for (uint32_t j = 0; j < N; ++j)
                 if (u0 + j < n_units_u && L::lane(px[j].has))
-                    a.running[u0 + j] = (uint8_t)frame_value_u8(lean_bd_from_thr(f32_to_bits(px[j].thr0)),
-                                                                f32_as_u32(px[j].bdt0), (double)sc.ref_time);
+                    a.running[u0 + j] = (uint8_t)view_value_u8(lean_bd_from_thr(f32_to_bits(px[j].thr0)),
+                                                                f32_as_u32(px[j].bdt0), 0u, 0u, view_intensity(sc.ref_time));
         }
     }
 }
@@ -2109,7 +2116,7 @@ __device__ __forceinline__ void rr_run_segment(const BatchArgs *__restrict__ b, 
 #pragma unroll
             for (uint32_t j = 0; j < N; ++j)
                 if (u0 + j < n_units_u && hdr_m(hdrv[j]) != 0u)
-                    a.running[u0 + j] = (uint8_t)frame_value_u8((hdrv[j] >> kHdrBdShift) & 0xffu, f32_as_u32(bv[j]), (double)a.sc.ref_time);
+                    a.running[u0 + j] = (uint8_t)view_value_u8((hdrv[j] >> kHdrBdShift) & 0xffu, f32_as_u32(bv[j]), 0u, 0u, view_intensity(a.sc.ref_time));
         }
     }
 }
@@ -2176,7 +2183,7 @@ struct EmitStage {
     }
 };
 
-template <bool ABS_T>
+template <bool ABS_T, bool VIEW = false>  // VIEW: as for adder_frame_kernel (last_fired_t is resident in both time modes here)
 __global__ __launch_bounds__(kBlockThreads) void adder_cont_kernel(const BatchArgs *__restrict__ b, uint32_t f0,
                                                                    uint32_t nb) {
     constexpr uint32_t N = kUnitsPerLane;
@@ -2206,7 +2213,11 @@ __global__ __launch_bounds__(kBlockThreads) void adder_cont_kernel(const BatchAr
                 a.lastf[u] = s.lastf;
                 if (a.running) {  // side plane (video.rs:713-730): the root's best event, if it has one
                     const ANode r = acc.load(0);
-                    if (r.has_best) a.running[u] = (uint8_t)frame_value_u8(r.bd, f32_as_u32(r.bdt), (double)a.sc.ref_time);
+                    if (r.has_best)
+                        a.running[u] = (uint8_t)view_value_u8(r.bd, f32_as_u32(r.bdt),
+                                                              VIEW ? f32_as_u32(fadd(a.sc.running_t, a.sc.time_spanned)) : 0u,
+                                                              VIEW ? f32_as_u32(s.lastf) : 0u,
+                                                              VIEW ? b->view : view_intensity(a.sc.ref_time));
                 }
             }
             seg[lane * N + j] = (uint8_t)cnt;
@@ -3375,6 +3386,8 @@ __global__ __launch_bounds__(kBlockThreads) void adder_feature_kernel(const Batc
                     if (fast9_is_feature(img, a.width, fa.plane_h, a.channels, x, gy)) {
                         is_new = *member == 0u;
                         *member = 1u;
+                        // "inserted during this frame" (new_features, video.rs:910-912), for ShowFeatureMode::Instant
+                        if (is_new && fa.stamp) fa.stamp[(size_t)(gy - a.row_begin) * a.width + x] = fa.stamp_base + f;
                     } else {
                         *member = 0u;
                     }
@@ -3632,10 +3645,15 @@ extern "C" hipError_t adder_launch_frame(const BatchArgs *b, uint32_t f, uint32_
     const uint32_t S = (num_waves + kWavesPerBlock - 1) / kWavesPerBlock;  // step workgroups
     const unsigned kernel = variant_frame_kernel(variant);
     if (kernel == ADDER_KERNEL_CONTINUOUS) {
-        if (abs_t) hipLaunchKernelGGL((adder_cont_kernel<true>), dim3(S), dim3(kBlockThreads), 0, stream, b, f, nb);
+        if (variant & kVarView) {
+            if (abs_t) hipLaunchKernelGGL((adder_cont_kernel<true, true>), dim3(S), dim3(kBlockThreads), 0, stream, b, f, nb);
+            else hipLaunchKernelGGL((adder_cont_kernel<false, true>), dim3(S), dim3(kBlockThreads), 0, stream, b, f, nb);
+        } else if (abs_t) hipLaunchKernelGGL((adder_cont_kernel<true>), dim3(S), dim3(kBlockThreads), 0, stream, b, f, nb);
         else hipLaunchKernelGGL((adder_cont_kernel<false>), dim3(S), dim3(kBlockThreads), 0, stream, b, f, nb);
         return hipGetLastError();
     }
+    // the D / DeltaT / SAE views of the side plane: no other kernel serves them (adder_batch_plan.hpp side_view)
+    if ((variant & kVarView) && kernel != ADDER_KERNEL_GENERIC) return hipErrorInvalidValue;
     if (kernel == ADDER_KERNEL_RUN_RECORDS) {  // (the bounded Collapse regime at c_thresh 0, integer state)
         const uint32_t SG = grid_cap && grid_cap < S ? grid_cap : S;
         if (abs_t) hipLaunchKernelGGL((adder_rr_kernel<true>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb, lazy);
@@ -3656,7 +3674,15 @@ extern "C" hipError_t adder_launch_frame(const BatchArgs *b, uint32_t f, uint32_
     }
     if (kernel == ADDER_KERNEL_GENERIC) {
         const uint32_t SG = grid_cap && grid_cap < S ? grid_cap : S;
-        if (collapse) {
+        if (variant & kVarView) {
+            if (collapse) {
+                if (abs_t) hipLaunchKernelGGL((adder_frame_kernel<true, true, true>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb);
+                else hipLaunchKernelGGL((adder_frame_kernel<true, false, true>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb);
+            } else {
+                if (abs_t) hipLaunchKernelGGL((adder_frame_kernel<false, true, true>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb);
+                else hipLaunchKernelGGL((adder_frame_kernel<false, false, true>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb);
+            }
+        } else if (collapse) {
             if (abs_t) hipLaunchKernelGGL((adder_frame_kernel<true, true>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb);
             else hipLaunchKernelGGL((adder_frame_kernel<true, false>), dim3(SG), dim3(kBlockThreads), 0, stream, b, f, nb);
         } else {

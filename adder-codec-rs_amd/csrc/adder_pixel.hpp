@@ -2124,6 +2124,44 @@ ADDER_HD uint32_t f32_as_u8(float val) {
 // framer/scale_intensity.rs:58-72): ((2^d / t) * ref_time) as u8 in f64.
 ADDER_HD uint32_t frame_value_u8(uint32_t d, uint32_t t, double tpf) { return f64_as_u8(event_intensity_f64(d, t) * tpf); }
 
+// What a byte of a u8 plane shows: FramedViewMode (video.rs:144-158), <u8 as FrameValue>::get_frame_value of a U8
+// source (framer/scale_intensity.rs:54-104).  ONE function for the transcoder's running_intensities side plane
+// (Video::instantaneous_view_mode, video.rs:331, 713-730) and for the framer (adder_framer.hpp framer_value_u8).
+constexpr uint32_t kViewIntensity = 0, kViewD = 1, kViewDeltaT = 2, kViewSae = 3;
+struct ViewConsts {
+    uint32_t view_mode;     // kView*
+    uint32_t ref_time;      // the `tpf` argument of get_frame_value (Intensity)
+    uint32_t delta_t_max;   // DeltaT / SAE
+    float practical_d_max;  // D: supplied by the caller (include/adder_framer.h)
+};
+ADDER_HD ViewConsts view_intensity(uint32_t ref_time) { return ViewConsts{kViewIntensity, ref_time, 0u, 0.0f}; }
+// d, t: the event (t = delta_t as u32); clock / prev_clock: the SAE pair -- the transcoder's running_t after the
+// frame's integrate and last_fired_t, both `as u32` (the subtraction wraps, as the release build does); the framer's
+// pixel clock after / before the event.  Every float -> int cast is Rust's `as`: saturating, NaN -> 0.
+ADDER_HD uint32_t view_value_u8(uint32_t d, uint32_t t, uint32_t clock, uint32_t prev_clock, const ViewConsts &k) {
+    if (k.view_mode == kViewD) return f32_as_u8((float)d / k.practical_d_max * 255.0f);
+    if (k.view_mode == kViewDeltaT) return f32_as_u8((float)t / (float)k.delta_t_max * 255.0f);
+    if (k.view_mode == kViewSae) return f32_as_u8((float)(clock - prev_clock) / (float)k.delta_t_max * 255.0f);
+    return frame_value_u8(d, t, (double)k.ref_time);
+}
+
+// Video::display_frame_features (video.rs:742-744, 1062-1088): draw_feature_coord (utils/viz.rs:94-120) stores 255 at
+// (y +- i, x) and (y, x +- i), i = 0..2, on channel 0 of a one-channel plane and channels 0..2 of any other.  As a
+// gather: is byte (x, y, c) of a w x h x channels plane under the cross of a member of m ([h][w], != 0 = member)?
+// Lookups are clamped to the plane (the product's features lie >= 3 from the border; the test's need not).
+constexpr int kCrossReach = 2;
+ADDER_HD bool display_drawn_channel(uint32_t c, uint32_t channels) { return channels == 1u ? c == 0u : c < 3u; }
+template <class Member>
+ADDER_HD bool display_under_cross(const Member &m, uint32_t w, uint32_t h, uint32_t x, uint32_t y) {
+    bool hit = false;
+    for (int i = -kCrossReach; i <= kCrossReach; ++i) {
+        const int xx = (int)x + i, yy = (int)y + i;
+        if (xx >= 0 && xx < (int)w) hit = hit || m((uint32_t)xx, y);
+        if (yy >= 0 && yy < (int)h) hit = hit || m(x, (uint32_t)yy);
+    }
+    return hit;
+}
+
 // ------------------------------------------------------------------------------------------
 // Feature-driven rate control.  FAST 9_16 corner test on the running-intensities plane
 // (utils/cv.rs:56-212, the OpenCV-style scan with its quick rejects): the reference's answer is exactly

@@ -72,7 +72,8 @@ __global__ __launch_bounds__(256) void adder_sparse_keys_kernel(const SparseStep
     idx[i] = i;
 }
 
-template <bool ABS_T>
+// VIEW: the side plane shows D, DeltaT or SAE (SparseArgs::view); the other instantiations are the code they were
+template <bool ABS_T, bool VIEW = false>
 __global__ __launch_bounds__(256) void adder_sparse_run_kernel(const SparseStep *__restrict__ steps, uint32_t n,
                                                                SparseArgs a, const uint32_t *__restrict__ keys,
                                                                const uint32_t *__restrict__ idx,
@@ -115,7 +116,9 @@ __global__ __launch_bounds__(256) void adder_sparse_run_kernel(const SparseStep 
         if (a.running && !(st.pad & 1u)) {
             const ANode r = acc.load(0);
             if (r.has_best) {
-                side = frame_value_u8(r.bd, f32_as_u32(r.bdt), (double)sc.ref_time);
+                // (rt: the pixel's running_t after this step's integrate; s.lastf: last_fired_t)
+                side = view_value_u8(r.bd, f32_as_u32(r.bdt), VIEW ? f32_as_u32(rt) : 0u, VIEW ? f32_as_u32(s.lastf) : 0u,
+                                     VIEW ? a.view : view_intensity(sc.ref_time));
                 side_set = true;
             }
         }
@@ -182,7 +185,13 @@ extern "C" hipError_t adder_sparse_run(const SparseArgs *args, const SparseStep 
     hipcub::DoubleBuffer<uint32_t> k(keys0, keys1), v(idx0, idx1);
     hipError_t e = hipcub::DeviceRadixSort::SortPairs(d_temp, temp_bytes, k, v, (int)n, 0, 32, stream);
     if (e != hipSuccess) return e;
-    if (a.sc.abs_t)
+    if (a.view.view_mode != kViewIntensity && a.sc.abs_t)
+        hipLaunchKernelGGL((adder_sparse_run_kernel<true, true>), dim3(grid), dim3(256), 0, stream, d_steps, n, a, k.Current(),
+                           v.Current(), stage, count);
+    else if (a.view.view_mode != kViewIntensity)
+        hipLaunchKernelGGL((adder_sparse_run_kernel<false, true>), dim3(grid), dim3(256), 0, stream, d_steps, n, a, k.Current(),
+                           v.Current(), stage, count);
+    else if (a.sc.abs_t)
         hipLaunchKernelGGL((adder_sparse_run_kernel<true>), dim3(grid), dim3(256), 0, stream, d_steps, n, a, k.Current(),
                            v.Current(), stage, count);
     else

@@ -24,6 +24,7 @@ constexpr uint32_t kVarWire = 1024u;        // the expansion writes the raw sink
 constexpr uint32_t kVarLazyState = 2048u;   // more launches of this batch follow (variant_lazy_state_bit)
 constexpr uint32_t kVarPacked = 4096u;      // lean runs in packed bytes (adder_lp_kernel / adder_lpx_kernel)
 constexpr uint32_t kVarPackedRgb = 8192u;   // ... on a three-channel plane (11-byte wire records)
+constexpr uint32_t kVarView = 16384u;       // the side plane shows D, DeltaT or SAE: the kernels' view instantiations
 constexpr uint32_t kVarKeyMask = 0xffffu;   // the bits the graph cache key holds
 
 // The frame kernel a variant runs (ADDER_KERNEL_*), in adder_launch_frame's order of precedence.

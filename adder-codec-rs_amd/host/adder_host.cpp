@@ -432,10 +432,42 @@ void Video::update_crf(uint8_t crf) {
     }
 }
 
-void Video::update_detect_features(bool detect_features, ShowFeatureMode, bool feature_rate_adjustment, bool) {
+void Video::update_detect_features(bool detect_features, ShowFeatureMode show_features, bool feature_rate_adjustment, bool) {
     feature_detection_ = detect_features;
+    show_features_ = show_features;
     feature_rate_adjustment_ = feature_rate_adjustment;
-    if (ctx_) sync_feature_controls();
+    if (ctx_) {
+        sync_feature_controls();
+        sync_view_controls();
+    }
+}
+
+Video &Video::instantaneous_view_mode(FramedViewMode view) {
+    view_mode_ = view;
+    if (ctx_) sync_view_controls();
+    return *this;
+}
+
+Video &Video::practical_d_max(std::optional<float> v) {
+    practical_d_max_ = v;
+    if (ctx_) sync_view_controls();
+    return *this;
+}
+
+// the device context's copy of {instantaneous_view_mode, show_features}.  The reference keeps running_intensities at all
+// times; here the plane costs the temporal blocking, so it is switched on by whoever asks for a view or a display.
+void Video::sync_view_controls() {
+    if (view_mode_ != FramedViewMode::Intensity || show_features_ != ShowFeatureMode::Off)
+        hip_check(ctx_, adder_hip_enable_running_intensities(ctx_, 1));
+    hip_check(ctx_, adder_hip_set_view_mode(ctx_, (uint32_t)view_mode_, practical_d_max_.value_or(0.0f)));
+    hip_check(ctx_, adder_hip_set_show_features(ctx_, (uint32_t)show_features_));
+}
+
+std::vector<uint8_t> Video::display_frame_features() {
+    ensure_ctx();
+    std::vector<uint8_t> out(plane_.volume());
+    hip_check(ctx_, adder_hip_display_frame(ctx_, out.data()));
+    return out;
 }
 
 void Video::update_roi(std::optional<Roi> roi) {
@@ -508,6 +540,7 @@ void Video::ensure_ctx() {
         px_c_thresh_reset_.reset();
     }
     if (pixel_tree_mode_ == Mode::FramePerfect) sync_feature_controls();
+    sync_view_controls();
 }
 
 std::vector<std::vector<Event>> Video::integrate_matrix(const Frame &matrix, float time_spanned) {

@@ -180,8 +180,9 @@ class Decoder {  // decoder.rs:22-29
     std::vector<Event> decoded_;  // compressed: all events of the stream, in stream order
 };
 
-// utils/viz.rs:76-86 -- display only; kept so that update_detect_features reads like the reference's
+// utils/viz.rs:76-86: which features Video::display_frame_features draws
 enum class ShowFeatureMode { Off, Instant, Hold };
+enum class FramedViewMode { Intensity, D, DeltaT, SAE };  // video.rs:144-158
 struct Roi {  // video.rs:219-223: start / end coordinates, inclusive
     uint16_t start_x = 0, start_y = 0, end_x = 0, end_y = 0;
 };
@@ -208,14 +209,23 @@ class Video {
     void update_crf(uint8_t crf);      // :1241-1251
     void update_quality_manual(uint8_t c_thresh_baseline, uint8_t c_thresh_max, uint32_t delta_t_max_multiplier,
                                uint8_t c_increase_velocity, float feature_c_radius);  // :1264-1287
-    // :825-837 -- feature detection on the running intensities + c_thresh reset around new features
-    // (show_features / feature_cluster drive displays and are not kept)
+    // :825-837 -- feature detection on the running intensities + c_thresh reset around new features; show_features
+    // selects the crosses of display_frame_features().  feature_cluster is not built: the reference's DBSCAN walks a
+    // HashSet in unspecified order and draws rand::random colours -- its output has no defined bytes.
     void update_detect_features(bool detect_features, ShowFeatureMode show_features, bool feature_rate_adjustment,
                                 bool feature_cluster);
     void update_roi(std::optional<Roi> roi);  // :1291-1293
     // VideoState::features as a membership plane [h][w] (1 = feature), running_intensities [h][w][c]
     std::vector<uint8_t> feature_set();
     std::vector<uint8_t> running_intensities();
+    // Video::instantaneous_view_mode (:331): what running_intensities holds -- and what FAST reads -- from the next frame on
+    Video &instantaneous_view_mode(FramedViewMode view);
+    // the D view's divisor: the reference's fast_math::log2_raw(255 * (delta_t_max / ref_time)) is an approximation the
+    // caller may supply (include/adder_framer.h); nullopt (default): the exact log2 of the same argument, recomputed
+    // when delta_t_max changes
+    Video &practical_d_max(std::optional<float> v);
+    // Video::display_frame_features (:328, 742-744, 1062-1088) after the last integrated frame, [h][w][c]
+    std::vector<uint8_t> display_frame_features();
     EncoderOptions get_encoder_options() const { return encoder_->options; }
     TimeMode get_time_mode() const { return encoder_->meta().time_mode; }
     uint8_t get_event_size() const { return encoder_->meta().event_size; }
@@ -238,7 +248,11 @@ class Video {
   private:
     void ensure_ctx();  // (re)creates the device context once every builder call has been made
     void sync_feature_controls();
+    void sync_view_controls();
     bool feature_detection_ = false, feature_rate_adjustment_ = false;
+    ShowFeatureMode show_features_ = ShowFeatureMode::Off;
+    FramedViewMode view_mode_ = FramedViewMode::Intensity;
+    std::optional<float> practical_d_max_;
     std::optional<Roi> roi_;
     PlaneSize plane_;
     int device_id_;
@@ -411,7 +425,6 @@ class Davis : public Source {
 // ---------------------------------------------------------------- framer (framer/driver.rs)
 enum class FramerMode { INSTANTANEOUS, INTEGRATION };  // driver.rs:20-28; stored, never read by the reference's ingest: both behave alike
 enum class SourceType { U8, U16, U32, U64 };           // what the Intensity view divides by (scale_intensity.rs:68-75); F32 / F64 panic there
-enum class FramedViewMode { Intensity, D, DeltaT, SAE };  // video.rs:144-158
 
 class FrameSequence;
 using FrameSequenceU8 = FrameSequence;

@@ -119,6 +119,48 @@ long long adder_host_transcode_features(const uint8_t *frames, uint32_t num_fram
     }
 }
 
+// Video with the transcoder UI's live view (adder-viz/src/transcoder/adder.rs:257, 351-354): instantaneous_view_mode,
+// update_detect_features(detect, show_features, ..) and, after `num_frames` integrate_matrix calls of gray or colour
+// frames ([T][h][w][channels] u8), running_intensities and display_frame_features ([h][w][channels] each; either may
+// be null).  practical_d_max <= 0: the mirror's default.  Returns the number of events, or -1.
+long long adder_host_live_view(const uint8_t *frames, uint32_t num_frames, uint16_t width, uint16_t height, uint8_t channels,
+                               uint32_t ref_time, uint32_t delta_t_max, int time_mode, uint32_t chunk_rows, int view_mode,
+                               float practical_d_max, int detect_features, int show_features, uint8_t *running_out,
+                               uint8_t *display_out) {
+    try {
+        if (view_mode < 0 || view_mode > 3 || show_features < 0 || show_features > 2)
+            throw SourceError(SourceError::BadParams, "bad view mode / ShowFeatureMode");
+        if (!frames && num_frames) throw SourceError(SourceError::BadParams, "null frames");
+        const PlaneSize plane(width, height, channels);
+        Video video(plane, nullptr);
+        video.chunk_rows(chunk_rows ? chunk_rows : 1);
+        video.time_parameters(ref_time * 30u, ref_time, delta_t_max, (TimeMode)time_mode);
+        video.write_out(SourceCamera::FramedU8, (TimeMode)time_mode, PixelMultiMode::Collapse, std::nullopt, EncoderType::Empty,
+                        EncoderOptions::default_(plane), nullptr);
+        video.instantaneous_view_mode((FramedViewMode)view_mode);
+        if (practical_d_max > 0.0f) video.practical_d_max(practical_d_max);
+        video.update_detect_features(detect_features != 0, (ShowFeatureMode)show_features, false, false);
+        long long total = 0;
+        const size_t fsz = plane.volume();
+        for (uint32_t k = 0; k < num_frames; ++k) {
+            const Frame f(frames + k * fsz, frames + (k + 1) * fsz);
+            for (auto &v : video.integrate_matrix(f, (float)ref_time)) total += (long long)v.size();
+        }
+        if (running_out) {
+            const std::vector<uint8_t> r = video.running_intensities();
+            memcpy(running_out, r.data(), r.size());
+        }
+        if (display_out) {
+            const std::vector<uint8_t> d = video.display_frame_features();
+            memcpy(display_out, d.data(), d.size());
+        }
+        return total;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+
 // Prophesee::new(ref_time, file) + consume() until the input runs out (prophesee.rs), with the decoded DVS events handed
 // over in memory instead of a `.dat` file: dvs = n records {t u32, x u16, y u16, p u8, pad u8}.  out receives the
 // events of every consume() in order, then those of end_events(); *n_consumes = consume() calls that returned events.

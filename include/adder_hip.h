@@ -115,7 +115,9 @@ int adder_hip_reset_c_thresh(AdderHipCtx *ctx, uint8_t c_thresh_baseline);
  * the generic kernels with one (c_thresh, c_increase_counter) pair per pixel, and steps frame by frame.  A context
  * that owns the whole plane does all of it inside the integrate call; a ROW BAND (multi-GPU) follows the protocol of
  * adder_hip_feature_detect below.
- * Video::update_detect_features (video.rs:825-837; show_features / feature_cluster only drive displays): */
+ * Video::update_detect_features (video.rs:825-837; its show_features argument: adder_hip_set_show_features below;
+ * feature_cluster is NOT built -- its DBSCAN walks a HashSet in unspecified order and draws rand::random colours, so its
+ * output has no defined bytes): */
 int adder_hip_update_detect_features(AdderHipCtx *ctx, int detect_features, int feature_rate_adjustment);
 /* CrfParameters::{c_thresh_baseline, feature_c_radius} (rate_controller.rs:40-53; update_quality_manual
  * video.rs:1264-1279).  Defaults: Crf::new(None) = quality 3: baseline 2, radius min(width, height) / 15. */
@@ -290,6 +292,35 @@ int adder_hip_enable_running_intensities(AdderHipCtx *ctx, int enable);
  * never enabled before a batch; a pending adder_hip_reset is applied first.  The context's next batch or reset waits
  * for the copy. */
 int adder_hip_running_intensities_device(AdderHipCtx *ctx, uint8_t *d_dst, void *stream);
+
+/* ---- the transcoder's live view (what the reference's UI shows, adder-viz/src/transcoder/adder.rs:257, 351-354) ----
+ * Video::instantaneous_view_mode (video.rs:331): ADDER_VIEW_* as in adder_framer.h.  practical_d_max: D view only,
+ * see adder_framer.h; <= 0: exact log2f(255 * (delta_t_max / ref_time)), recomputed when delta_t_max changes.
+ * Takes effect with the next integrated frame; bytes already in the plane stay until their unit is written again.
+ * The byte a unit gets after a frame in which its root holds a best event {d, delta_t} is <u8 as FrameValue>::
+ * get_frame_value (framer/scale_intensity.rs:54-104) -- Intensity as before, D = d / practical_d_max * 255, DeltaT =
+ * delta_t / delta_t_max * 255, SAE = (running_t - last_fired_t, wrapping u32) / delta_t_max * 255, each `as u8` -- and
+ * FAST reads the plane in whatever view it holds (video.rs:907), so the view changes which features are found.
+ * While the plane is on in the D, DeltaT or SAE view, dense batches run the generic frame kernel (Continuous contexts:
+ * theirs) in its view instantiation, and -- as after any generic batch -- stay generic until adder_hip_reset; the
+ * Intensity view and every batch with the plane off run what they ran before.  A DeltaT context keeps last_fired_t
+ * (event_pixel_tree.rs:257) only in those view batches: set the view before the first frame (or switch from D / DeltaT)
+ * for an SAE plane that equals the reference's; after Intensity batches it counts from 0 until the unit's next pop.
+ * Row bands take it too (the value is per pixel; the halo export carries whatever the plane holds). */
+int adder_hip_set_view_mode(AdderHipCtx *ctx, uint32_t view_mode, float practical_d_max);
+/* ShowFeatureMode (utils/viz.rs:76-86): 0 Off, 1 Instant, 2 Hold.  Refused (ADDER_E_BAD_PARAMS) on a row band unless 0:
+ * a cross reaches two rows into the neighbouring band. */
+int adder_hip_set_show_features(AdderHipCtx *ctx, uint32_t mode);
+/* Video::display_frame_features after the last integrated frame, [rows][width][channels] u8: the running plane, and
+ * with feature detection on a white cross (draw_feature_coord, utils/viz.rs:94-120: 255 at (y +- i, x), (y, x +- i), i =
+ * 0..2; channel 0 of a one-channel plane, channels 0..2 otherwise) on every feature (Hold) or on every feature the last
+ * integrated frame found new (Instant).  The reference overwrites the frame every frame: only this state is observable.
+ * _device: d_dst is device memory at ANY byte address; queued on `stream` (NULL: the default stream) behind everything
+ * the context has queued, no host synchronisation; the context's next batch or reset waits for it.
+ * ADDER_E_BAD_PARAMS if the plane was never enabled before a batch, and on a row band.  (After a rolled-back batch the
+ * Instant crosses are those of the next integrated frame.) */
+int adder_hip_display_frame(AdderHipCtx *ctx, uint8_t *dst_host);
+int adder_hip_display_frame_device(AdderHipCtx *ctx, uint8_t *d_dst, void *stream);
 
 /* Duration in milliseconds of the kernels of the last adder_hip_integrate_device
  * batch, measured with HIP events on the launch stream (0 if none). */
