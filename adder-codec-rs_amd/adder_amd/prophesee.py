@@ -56,6 +56,7 @@ SYMBOLS = {
     "adder_prophesee_finish_device": (_i32, [_vp, _vp, _u64, _pu64, _vp]),
     "adder_prophesee_finish_host": (_i32, [_vp, _vp, _u64, _pu64]),
     "adder_prophesee_state": (_i32, [_vp, _pu32, _pu32, _pu64, _pu64]),
+    "adder_prophesee_pixel_state": (_i32, [_vp, _vp, _vp]),
     "adder_prophesee_running_intensities": (_i32, [_vp, _vp]),
     "adder_prophesee_exp": (C.c_double, [C.c_double]),
     "adder_prophesee_exp_host": (None, [_vp, _vp, _u64]),
@@ -245,6 +246,13 @@ class HipProphesee:
         n = C.c_uint64(0)
         self._check(self.L.adder_prophesee_finish_host(self.h, out.ctypes.data, cap, C.byref(n)))
         return out[: n.value].copy()
+
+    def pixel_state(self):
+        """The camera state the last accepted push left -> (last t, last ln): (H, W) uint32 and float64 planes."""
+        t = np.zeros((self.height, self.width), np.uint32)
+        ln = np.zeros((self.height, self.width), np.float64)
+        self._check(self.L.adder_prophesee_pixel_state(self.h, t.ctypes.data, ln.ctypes.data))
+        return t, ln
 
     def running_intensities(self):
         out = np.zeros((self.height, self.width), np.uint8)

@@ -360,6 +360,15 @@ extern "C" int adder_prophesee_state(const AdderProphesee *v, uint32_t *running_
     return ADDER_OK;
 }
 
+extern "C" int adder_prophesee_pixel_state(AdderProphesee *v, uint32_t *last_t, double *last_ln) {
+    if (!v) return ADDER_E_BAD_PARAMS;
+    PHIPCHK(v, hipSetDevice(v->p.device_id));
+    // (every push and finish has waited for its stream before it returned)
+    if (last_t) PHIPCHK(v, hipMemcpy(last_t, v->a.cur_t, (size_t)v->a.units * 4u, hipMemcpyDeviceToHost));
+    if (last_ln) PHIPCHK(v, hipMemcpy(last_ln, v->a.cur_ln, (size_t)v->a.units * 8u, hipMemcpyDeviceToHost));
+    return ADDER_OK;
+}
+
 extern "C" int adder_prophesee_running_intensities(AdderProphesee *v, uint8_t *dst) {
     if (!v || !dst) return ADDER_E_BAD_PARAMS;
     const int rc = adder_hip_running_intensities(v->ctx, dst);

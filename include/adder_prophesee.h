@@ -112,6 +112,9 @@ int adder_prophesee_finish_host(AdderProphesee *pr, AdderEvent *out, uint64_t ou
 /* running_t, the open group's start, the records carried in the open group, the records pushed so far. */
 int adder_prophesee_state(const AdderProphesee *pr, uint32_t *running_t, uint32_t *group_start_t,
                           uint64_t *open_records, uint64_t *records_pushed);
+/* The camera state per pixel in raster order, as committed by the last accepted push: last t and last log intensity
+ * (W * H values each, host buffers; either may be NULL). */
+int adder_prophesee_pixel_state(AdderProphesee *pr, uint32_t *last_t, double *last_ln);
 /* The running-intensities side plane (H * W bytes), host buffer. */
 int adder_prophesee_running_intensities(AdderProphesee *pr, uint8_t *dst);
 

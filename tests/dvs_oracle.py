@@ -4,6 +4,9 @@ reference's u128), intensities go through math.log1p (the same libm log1p Rust's
 
 Errors follow the library's definition: the first event of a unit with d > 128, any event with d in 129..=254 and
 any event outside the plane stop the run; run() returns the output of the events before it and the event's index.
+
+DvsRestatement(.., census=c) also counts, per unit, the arms a run takes (tests/chain_arms.py names them); the output
+does not depend on it.
 """
 import math
 import struct
@@ -29,12 +32,13 @@ def intensity_ln(d, t, ref):
 
 
 class DvsRestatement:
-    def __init__(self, width, height, channels, time_mode, ref_interval, source_camera, theta=0.01):
+    def __init__(self, width, height, channels, time_mode, ref_interval, source_camera, theta=0.01, census=None):
         self.w, self.h, self.ch = width, height, channels
         self.delta_t = time_mode == DELTA_T
         self.ref = ref_interval
         self.framed = is_framed(source_camera)
         self.theta = theta
+        self.census = census
         self.px = {}  # (y, x, c) -> [d, frame_intensity_ln, t]
 
     @classmethod
@@ -46,7 +50,7 @@ class DvsRestatement:
         """events: iterable of (x, y, c, d, t) (c 0xFF = None) or an EVENT_DTYPE array.  units: optional set of
         (y, x, c) to restrict the state to (units are independent).  -> (list of (t, x, y, p), bad index or None)."""
         out = []
-        ref, theta = self.ref, self.theta
+        ref, theta, cen = self.ref, self.theta, self.census
         win_hi = math.log1p(1.0) - theta
         win_lo = math.log1p(0.0) + theta
         half = theta / 2.0
@@ -66,21 +70,34 @@ class DvsRestatement:
                 if d > D_ZERO_INTEGRATION:
                     return out, k
                 self.px[u] = [d, intensity_ln(d, t, ref), t]
+                if cen is not None:
+                    cen.hit("first", u)
+                    cen.hit("d128" if d == D_ZERO_INTEGRATION else "t0" if t == 0 else "t_pos", u)
                 continue
             old_t = px[2]
             if self.delta_t:
                 px[2] += t
             else:
                 px[2] = t
+                if cen is not None and t < (old_t & 0xFFFFFFFF):
+                    cen.hit("abs_saturate", u)
                 t = max(0, t - (old_t & 0xFFFFFFFF))  # event.t.saturating_sub(old_t as u32)
             if self.framed and px[2] % ref != 0:
                 px[2] = (px[2] // ref + 1) * ref
+                if cen is not None:
+                    cen.hit("rounded", u)
             if d == D_EMPTY:
                 px[0] = d
+                if cen is not None:
+                    cen.hit("empty", u)
                 continue
             new = intensity_ln(d, t, ref)
             old = px[1]
             win = 0.406 < new < 0.407
+            if cen is not None:
+                cen.hit("d128" if d == D_ZERO_INTEGRATION else "t0" if t == 0 else "t_pos", u)
+                arm = _arm(win, new, old, px[2] == old_t, win_hi, win_lo, half)
+                cen.hit(arm, u)
             if win and (old > win_hi or (px[2] == old_t and old > 0.6)):
                 p = 1
             elif win and (old < win_lo or (px[2] == old_t and old < 0.3)):
@@ -91,11 +108,28 @@ class DvsRestatement:
                 p = 0
             else:
                 p = None
+            assert cen is None or _ARM_POLARITY[arm] == p
             if p is not None:
                 out.append((old_t + 1, x, y, p))
                 px[1] = new
             px[0] = d
         return out, None
+
+
+_ARM_POLARITY = dict(win_hi=1, win_same_hi=1, win_lo=0, win_same_lo=0, up=1, down=0, none=None)
+
+
+def _arm(win, new, old, same_t, win_hi, win_lo, half):
+    """census only: the name of the arm the four-way test of run() takes"""
+    if win and old > win_hi:
+        return "win_hi"
+    if win and same_t and old > 0.6:
+        return "win_same_hi"
+    if win and old < win_lo:
+        return "win_lo"
+    if win and same_t and old < 0.3:
+        return "win_same_lo"
+    return "up" if new > old + half else "down" if new < old - half else "none"
 
 
 def header_bytes(width, height, date, binary):

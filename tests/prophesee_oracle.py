@@ -3,7 +3,10 @@ decode_event, Prophesee::new / consume / end_events and the CLI's .crf(c), over 
 its sparse driver (integrate_for_px per step, in order).  f64 exp / ln_1p are libm's (math.exp, math.log1p).
 
 It is the yardstick of tests/test_prophesee_cpu.py and tests/test_gpu_prophesee.py; the reference has no .dat
-golden.  Where the reference panics, this raises: BadHeader, BadRecord(index), EndAssert."""
+golden.  Where the reference panics, this raises: BadHeader, BadRecord(index), EndAssert.
+
+Prophesee(.., census=c) also counts, per pixel, the arms of the chain a run takes (tests/chain_arms.py names them);
+the events do not depend on it."""
 import math
 
 import numpy as np
@@ -115,8 +118,11 @@ def _step(x, y, val, intensity, time, no_side):
 class Prophesee:
     """Prophesee::new(ref_time, ..)[.crf(c)] over decoded records; run() = consume() until the input ends."""
 
-    def __init__(self, width, height, ref_time, crf=None):
+    def __init__(self, width, height, ref_time, crf=None, census=None):
         self.W, self.H, self.ref_time = width, height, ref_time
+        self.census = census
+        # census only: a pixel's running time as its arena adds it up in f32 (the two start-up frames first)
+        self.acc_t = [np.float32(2 * ref_time)] * (width * height) if census is not None else None
         v = O.Video(width, height, 1, time_mode=O.ABSOLUTE_T, multi_mode=O.COLLAPSE, ref_time=ref_time,
                     delta_t_max=2 * ref_time)
         v.set_pixel_mode(1)
@@ -161,26 +167,46 @@ class Prophesee:
 
     def consume_batch(self, batch):
         """:172-258 for one group."""
-        steps, W, rt = [], self.W, self.ref_time
+        steps, W, rt, cen = [], self.W, self.ref_time, getattr(self, "census", None)
         for idx, t, x, y, p in batch:
             if x >= W or y >= self.H:
                 raise BadRecord(idx)  # ndarray indexing panics
             px = y * W + x
             last_t = self.last_t[px]
             if t < last_t:
+                if cen is not None:
+                    cen.hit("skip", px)
                 continue
             ln = self.last_ln[px]
             if t > ((last_t + 1) & M32):
                 val = (math.exp(ln) - 1.0) * 255.0
+                if cen is not None:
+                    cen.hit("gap", px)
+                    if val > 255.0:
+                        cen.hit("gap_clamp_hi", px)
+                    elif val < 0.0:
+                        cen.hit("gap_clamp_lo", px)
                 if val < 0.0 or val > 255.0:  # mid_clamp_u8
                     val, ln = 128.0, math.log1p(128.0 / 255.0)
                 gap = (t - last_t - 1) & M32
+                if cen is not None:
+                    if gap * rt > M32:
+                        cen.hit("gap_time_wrap", px)
+                    self._note_time(px, (gap * rt) & M32)
                 steps.append(_step(x, y, val, val * float(gap), (gap * rt) & M32, 1))
+            elif cen is not None:
+                cen.hit("same_t" if t == last_t else "step_no_gap", px)
             new_ln = ln - self.theta if p == 0 else ln + self.theta
             self.last_ln[px] = new_ln
             self.last_t[px] = t
             if t > last_t:
                 val = (math.exp(new_ln) - 1.0) * 255.0
+                if cen is not None:
+                    if val > 255.0:
+                        cen.hit("step_clamp_hi", px)
+                    elif val < 0.0:
+                        cen.hit("step_clamp_lo", px)
+                    self._note_time(px, rt)
                 if val < 0.0 or val > 255.0:
                     val, new_ln = 128.0, math.log1p(128.0 / 255.0)
                 self.last_ln[px] = new_ln
@@ -191,7 +217,7 @@ class Prophesee:
 
     def end_events(self):
         """:325-365, raster order, no clamp."""
-        steps = []
+        steps, cen = [], getattr(self, "census", None)
         for y in range(self.H):
             for x in range(self.W):
                 px = y * self.W + x
@@ -200,8 +226,19 @@ class Prophesee:
                 if not d > 0:
                     raise EndAssert("assert!(running_t - dvs_last_timestamps > 0)")
                 span = (d * self.ref_time) & M32
+                if cen is not None:
+                    if d * self.ref_time > M32:
+                        cen.hit("end_span_wrap", px)
+                    self._note_time(px, span)
                 steps.append(_step(x, y, val, val * float(span), span, 1))
         return self.v.integrate_sparse(np.array(steps, O.SPARSE_STEP_DTYPE))
+
+    def _note_time(self, px, time):
+        """census only: a step of `time` ticks on px; counts the steps and pixels past f32's exact range and 2^31"""
+        acc = self.acc_t[px] = np.float32(self.acc_t[px] + np.float32(time))
+        for arm, limit in (("t_over_2p24", 1 << 24), ("t_over_2p31", 1 << 31)):
+            if time > limit or acc > limit:
+                self.census.hit(arm, px)
 
     def running_intensities(self):
         return self.v.running_intensities()[:, :, 0]
