@@ -2189,11 +2189,14 @@ extern "C" int adder_hip_wire_scatter_device(AdderHipCtx *c, const AdderEvent *d
                                              uint64_t header_bytes, void *stream) {
     if (!c) return ADDER_E_BAD_PARAMS;
     if (!d_events || !d_frame_offsets || !d_dest || !out) return fail(c, ADDER_E_BAD_PARAMS, "wire scatter: null pointer");
+    // (the kernel takes a segment's dword phase from its byte OFFSET in the image: the image itself must start on a dword)
+    if ((((uintptr_t)d_events | (uintptr_t)out) & 3u) != 0u)
+        return fail(c, ADDER_E_BAD_PARAMS, "wire scatter: d_events and out must be 4-byte aligned");
     HIPCHK(c, hipSetDevice(c->device));
     // (the events per frame are known on the device only: a fixed grid of workgroups walks every frame's blocks)
     HIPCHK(c, adder_launch_wire_scatter(reinterpret_cast<const AdderEventPod *>(d_events), d_frame_offsets, num_frames, d_dest,
                                         wire_record_bytes(c), out, out_cap_bytes, header_bytes,
-                                        reinterpret_cast<uint32_t *>(c->d_side_words + 1), c->num_cus * 4u, (hipStream_t)stream));
+                                        reinterpret_cast<uint32_t *>(c->d_side_words + 1), c->num_cus * kScatterGroupsPerCu, (hipStream_t)stream));
     return ADDER_OK;
 }
 

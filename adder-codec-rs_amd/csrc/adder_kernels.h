@@ -46,6 +46,11 @@ constexpr uint32_t kLeanParkBytes = kWaveUnits * kLeanRecBytes;
 constexpr uint32_t kLeanPark8Bytes = kWaveUnits * kLeanRec8Bytes;
 __host__ __device__ constexpr uint32_t lean_rec_bytes(bool abs_t) { return abs_t ? kLeanRecBytes : kLeanRec8Bytes; }
 constexpr uint32_t kGenRecBytes = 8;                               // generic variants: one per EVENT
+// the stream hand-off kernels (wire serialiser, sink per rank, multi-GPU merge); tests/kernel_constants.py reads these
+constexpr uint32_t kWireEvents = 1024;        // events one workgroup of adder_wire_kernel / adder_wire_scatter_kernel converts at a time (a multiple of 4)
+constexpr uint32_t kScatterGroupsPerCu = 4;   // adder_wire_scatter_kernel's fixed grid: workgroups per compute unit
+constexpr uint32_t kMergeTileFrames = 256;    // frames adder_merge_layout_kernel prefixes per tile (its block size)
+constexpr uint32_t kMaxGridRows = 65535;      // gridDim.y at most: adder_merge_copy_kernel walks the (rank, frame) pairs past it
 
 // bits of the device status word
 constexpr uint32_t kStatusCapacity = 1u;  // an event did not fit into the output buffer

@@ -3142,9 +3142,8 @@ extern "C" hipError_t adder_launch_expand_bands(const uint8_t *descs, uint32_t s
 // 12 bytes per event).  A workgroup converts kWireEvents events: coalesced dword loads into
 // LDS, per-event repack in LDS, coalesced dword stores of the record bytes (kWireEvents is a
 // multiple of 4, so every workgroup's output starts on a dword of the stream; `out` itself may be
-// any byte address: the store's type says so).
+// any byte address: the store's type says so).  kWireEvents: adder_kernels.h.
 // ------------------------------------------------------------------------------------------
-constexpr uint32_t kWireEvents = 1024;
 __global__ __launch_bounds__(256) void adder_wire_kernel(const uint32_t *__restrict__ ev, uint64_t n, uint32_t rec,
                                                          uint8_t *__restrict__ out, uint32_t *status) {
     __shared__ uint32_t s_w[kWireEvents * 3];
@@ -3445,7 +3444,7 @@ __global__ __launch_bounds__(kBlockThreads) void adder_feature_apply_kernel(cons
 // offsets (Vec<Vec<Event>> structure, video.rs:677-691) and the result header.  d_offsets[0..1] = the frame's
 // range in d_ev.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adder_frame_out_kernel(const AdderEventPod *__restrict__ d_ev,
+__global__ __launch_bounds__(kBlockThreads) void adder_frame_out_kernel(const AdderEventPod *__restrict__ d_ev,
                                                               const uint64_t *__restrict__ d_offsets, uint64_t cap,
                                                               AdderEventPod *__restrict__ h_ev, FrameResult *h_res,
                                                               uint32_t *__restrict__ h_chunks,
@@ -3472,7 +3471,7 @@ __global__ __launch_bounds__(256) void adder_frame_out_kernel(const AdderEventPo
         }
         return;
     }
-    const uint32_t c = (blockIdx.x - copy_blocks) * 256u + threadIdx.x;
+    const uint32_t c = (blockIdx.x - copy_blocks) * kBlockThreads + threadIdx.x;
     if (c == 0) {
         h_res->produced = produced;
         h_res->status = *status | (produced > cap ? kStatusCapacity : 0u);
@@ -3508,12 +3507,12 @@ __global__ __launch_bounds__(256) void adder_frame_out_kernel(const AdderEventPo
 // the lower ranks).  Two launches: the layout (one block), then the copy.
 // work layout (uint64): [0, T] merged frame offsets, then dst[r][f] for r < world, f < T.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adder_merge_layout_kernel(const uint64_t *__restrict__ offs, uint32_t world,
+__global__ __launch_bounds__(kMergeTileFrames) void adder_merge_layout_kernel(const uint64_t *__restrict__ offs, uint32_t world,
                                                                  uint32_t T, uint64_t *__restrict__ work,
                                                                  uint64_t *__restrict__ merged_offsets,
                                                                  uint64_t merged_base) {
-    // frame totals -> exclusive prefix over frames (serial per 256-frame tile; T is a few hundred)
-    __shared__ uint64_t s_tile[256];
+    // frame totals -> exclusive prefix over frames (serial per tile of kMergeTileFrames = 256 frames; T is a few hundred)
+    __shared__ uint64_t s_tile[kMergeTileFrames];
     __shared__ uint64_t s_carry;
     const uint32_t tid = threadIdx.x;
     if (tid == 0) {
@@ -3522,7 +3521,7 @@ __global__ __launch_bounds__(256) void adder_merge_layout_kernel(const uint64_t 
         if (merged_offsets) merged_offsets[0] = merged_base;  // (a chunk of a longer stream: the events before it)
     }
     __syncthreads();
-    for (uint32_t f0 = 0; f0 < T; f0 += 256u) {
+    for (uint32_t f0 = 0; f0 < T; f0 += kMergeTileFrames) {
         const uint32_t f = f0 + tid;
         uint64_t tot = 0;
         if (f < T)
@@ -3531,7 +3530,7 @@ __global__ __launch_bounds__(256) void adder_merge_layout_kernel(const uint64_t 
         __syncthreads();
         if (tid == 0) {
             uint64_t run = s_carry;
-            for (uint32_t k = 0; k < 256u; ++k) {
+            for (uint32_t k = 0; k < kMergeTileFrames; ++k) {
                 const uint64_t t = s_tile[k];
                 s_tile[k] = run;  // exclusive
                 run += t;
@@ -3559,7 +3558,7 @@ __global__ __launch_bounds__(256) void adder_merge_copy_kernel(const uint32_t *_
                                                                uint32_t T, const uint64_t *__restrict__ work,
                                                                uint32_t *__restrict__ out, uint64_t out_cap,
                                                                uint32_t *status) {
-    // (rank, frame) pairs: blockIdx.y walks them (world * T may exceed the 65 535 rows a grid can have)
+    // (rank, frame) pairs: blockIdx.y walks them (world * T may exceed the kMaxGridRows = 65 535 rows a grid can have)
     for (uint32_t rf = blockIdx.y; rf < world * T; rf += gridDim.y) {
         const uint32_t r = rf / T, f = rf - r * T;
         uint64_t stage_base = 0;
@@ -3960,7 +3959,7 @@ extern "C" hipError_t adder_launch_fill_u32(uint32_t *p, size_t n, uint32_t v, h
 extern "C" hipError_t adder_launch_chunk_offsets(const AdderEventPod *ev, uint32_t n, uint32_t row_begin,
                                                  uint32_t chunk_rows, uint32_t num_chunks, uint32_t *offsets,
                                                  hipStream_t stream) {
-    const uint32_t bs = 256;
+    const uint32_t bs = kBlockThreads;
     hipLaunchKernelGGL(adder_chunk_offsets_kernel, dim3((num_chunks + 1 + bs - 1) / bs), dim3(bs), 0, stream, ev,
                        n, row_begin, chunk_rows, num_chunks, offsets);
     return hipGetLastError();
@@ -3973,8 +3972,8 @@ extern "C" hipError_t adder_launch_frame_out(const AdderEventPod *d_ev, const ui
     // a slice of the chip keeps a x16 link busy (null: the wire scatter did the hand-over); ADDER_HIP_OUT_BLOCKS for A/Bs
     static const uint32_t want_blocks = [] { const char *e = getenv("ADDER_HIP_OUT_BLOCKS"); return e ? (uint32_t)atoi(e) : 128u; }();
     const uint32_t copy_blocks = h_ev ? (want_blocks ? want_blocks : 128u) : 0;
-    const uint32_t chunk_blocks = (num_chunks + 1 + 255) / 256;
-    hipLaunchKernelGGL(adder_frame_out_kernel, dim3(copy_blocks + chunk_blocks), dim3(256), 0, stream, d_ev, d_offsets,
+    const uint32_t chunk_blocks = (num_chunks + 1 + kBlockThreads - 1) / kBlockThreads;
+    hipLaunchKernelGGL(adder_frame_out_kernel, dim3(copy_blocks + chunk_blocks), dim3(kBlockThreads), 0, stream, d_ev, d_offsets,
                        cap, h_ev, h_res, h_chunks, status, counters, row_begin, chunk_rows, num_chunks, copy_blocks, wire_rec);
     return hipGetLastError();
 }
@@ -4008,10 +4007,10 @@ extern "C" hipError_t adder_launch_merge(const adder::AdderEventPod *stage, cons
                                          uint64_t *work, adder::AdderEventPod *out, uint64_t out_cap,
                                          uint64_t *merged_offsets, uint64_t merged_base, uint32_t *status, hipStream_t stream) {
     if (world == 0 || T == 0) return hipSuccess;
-    hipLaunchKernelGGL(adder_merge_layout_kernel, dim3(1), dim3(256), 0, stream, offs, world, T, work, merged_offsets,
+    hipLaunchKernelGGL(adder_merge_layout_kernel, dim3(1), dim3(kMergeTileFrames), 0, stream, offs, world, T, work, merged_offsets,
                        merged_base);
     const uint64_t pairs = (uint64_t)world * T;
-    hipLaunchKernelGGL(adder_merge_copy_kernel, dim3(64, (uint32_t)(pairs < 65535u ? pairs : 65535u)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(adder_merge_copy_kernel, dim3(64, (uint32_t)(pairs < kMaxGridRows ? pairs : kMaxGridRows)), dim3(256), 0, stream,
                        reinterpret_cast<const uint32_t *>(stage), offs, world, T, work,
                        reinterpret_cast<uint32_t *>(out), out_cap, status);
     return hipGetLastError();

@@ -442,6 +442,9 @@ int adder_hip_expand_status(AdderHipCtx *root, void *stream);
  * wire records at out + header_bytes + d_dest[f] * record_bytes.  `out` is anything the device can store to: HBM, or host
  * memory mapped into the device (hipHostRegister / hipHostMalloc) -- then the stores cross this GPU's own PCIe link and
  * the bytes land where the file has them.  Bytes past out_cap_bytes are dropped and reported by adder_hip_expand_status.
+ * `out` and d_events must be 4-byte aligned (ADDER_E_BAD_PARAMS otherwise, nothing queued): a segment is stored as leading
+ * bytes, whole dwords and trailing bytes, split by the phase of its byte OFFSET in the image (header_bytes + d_dest[f] *
+ * record_bytes, which may have any phase), so the image itself has to start on a dword.
  * Both queue on `stream`; nothing waits on the host. */
 int adder_hip_sink_layout_device(AdderHipCtx *ctx, const uint64_t *d_all_offsets, uint32_t world, uint32_t rank,
                                  uint32_t num_frames, uint64_t *d_file_pos, uint64_t *d_dest, uint64_t *d_merged_offsets,

@@ -158,3 +158,37 @@ def test_records_pipelined_gather_single_rank_through_the_wire_image(time_mode):
         merged, moff = rg.result()
         assert merged.shape[0] == n_want and torch.equal(moff, d_off)
         assert merged.cpu().numpy().tobytes() == d_ev[:n_want].cpu().numpy().tobytes()
+
+
+def test_wire_scatter_refuses_unaligned_pointers():
+    """adder_hip_wire_scatter_device takes a segment's dword phase from its byte offset in the image, so `out` (and
+    d_events, by its type) must be 4-byte aligned: anything else is ADDER_E_BAD_PARAMS, nothing is queued and the context
+    stays usable -- the aligned call then writes the records (tests/handoff_oracle.py) and nothing behind them."""
+    import torch
+    import handoff_cases as HC
+    import handoff_oracle as HO
+    A = _hip()
+    hv = A.HipVideo(16, 16, 1)
+    n = 40
+    ev = HC.make_events(0, np.zeros(n, np.int64), np.arange(n))
+    d_ev = torch.from_numpy(np.concatenate([ev, ev[:1]]).view(np.uint8)).cuda()
+    offs = torch.tensor([0, n], dtype=torch.int64, device="cuda")
+    dest = torch.zeros(1, dtype=torch.int64, device="cuda")
+    image = torch.full((9 * n + 64,), 0xEE, dtype=torch.uint8, device="cuda")
+
+    def scatter(e, o):
+        return hv.L.adder_hip_wire_scatter_device(hv.h, e, offs.data_ptr(), 1, dest.data_ptr(), o, 9 * n, 0, None)
+
+    assert d_ev.data_ptr() % 4 == 0 and image.data_ptr() % 4 == 0
+    for k in (1, 2, 3):
+        assert scatter(d_ev.data_ptr(), image.data_ptr() + k) == A.E_BAD_PARAMS
+        assert scatter(d_ev.data_ptr() + k, image.data_ptr()) == A.E_BAD_PARAMS
+    assert b"4-byte aligned" in hv.L.adder_hip_last_error(hv.h)
+    torch.cuda.synchronize()
+    assert bool((image == 0xEE).all().item())
+    assert scatter(d_ev.data_ptr(), image.data_ptr()) == A.OK
+    torch.cuda.synchronize()
+    assert image[: 9 * n].cpu().numpy().tobytes() == HO.wire_bytes(ev, 9).tobytes()
+    assert bool((image[9 * n:] == 0xEE).all().item())
+    hv.expand_status()
+    hv.close()
