@@ -68,7 +68,9 @@ __device__ __forceinline__ StreamEv stream_load(const void *in, uint64_t i) {
     return e;
 }
 
-// record i of `in` -> record i of `out` with its time replaced (out == in allowed: one thread owns the record)
+// record i of `in` -> record i of `out` with its time replaced (out == in allowed: one thread owns the record).
+// The WHOLE record: every byte other than the four of t is the input's, whichever tag -- a None record's t ends at
+// byte 9 and its byte 10 is carried like the rest.
 template <int SRC>
 __device__ __forceinline__ void stream_store(const void *in, void *out, uint64_t i, uint32_t t) {
     if (SRC == kStreamEvents) {
@@ -80,8 +82,10 @@ __device__ __forceinline__ void stream_store(const void *in, void *out, uint64_t
         const uint8_t *p = (const uint8_t *)in + i * rb;
         uint8_t *q = (uint8_t *)out + i * rb;
         const uint32_t off = SRC == kStreamWire9 ? 5u : wire11_t_offset(p[4]);
-        if (q != p)
+        if (q != p) {
             for (uint32_t k = 0; k < off; ++k) q[k] = p[k];
+            for (uint32_t k = off + 4u; k < rb; ++k) q[k] = p[k];
+        }
         q[off] = (uint8_t)(t >> 24);
         q[off + 1u] = (uint8_t)(t >> 16);
         q[off + 2u] = (uint8_t)(t >> 8);

@@ -182,6 +182,11 @@ extern "C" int adder_stream_create(const AdderStreamParams *p, AdderStream **out
                      ADDER_STREAM_ABI_VERSION);
     if (p->width == 0 || p->height == 0 || (p->channels != 1 && p->channels != 3))
         return sfail(nullptr, ADDER_E_BAD_PARAMS, "plane %ux%ux%u", p->width, p->height, p->channels);
+    // keys are 32 bits wide and the sentinel key is `units` itself: units + 1 keys have to fit
+    const uint64_t units64 = (uint64_t)p->width * p->height * p->channels;
+    if (units64 + 1u > (uint64_t)UINT32_MAX)
+        return sfail(nullptr, ADDER_E_BAD_PARAMS, "plane %ux%ux%u: %llu units and the sentinel key do not fit 32 bits",
+                     p->width, p->height, p->channels, (unsigned long long)units64);
     if (p->ref_interval == 0) return sfail(nullptr, ADDER_E_BAD_PARAMS, "ref_interval must be > 0");
     if (p->codec_version > 3 || p->time_mode > 2 || p->out_time_mode > 2)
         return sfail(nullptr, ADDER_E_BAD_PARAMS, "codec version %u, time modes %u -> %u", p->codec_version,
@@ -202,7 +207,7 @@ extern "C" int adder_stream_create(const AdderStreamParams *p, AdderStream **out
     a.width = p->width;
     a.height = p->height;
     a.channels = p->channels;
-    a.units = (uint32_t)p->width * p->height * p->channels;
+    a.units = (uint32_t)units64;
     a.key_bits = 1;
     while ((1ull << a.key_bits) < (uint64_t)a.units + 1u) ++a.key_bits;  // keys 0..units (units: never worked on)
     a.ref = p->ref_interval;

@@ -23,6 +23,9 @@
  *   anything else (equal modes, Mixed on either side): events pass through unchanged and no state moves, which is
  *       what migrate_v2 does with an output mode other than AbsoluteT.
  *   x, y, c, d pass through; a migrated stream has exactly as many events as its input, so d_out == d_in is allowed.
+ *   An output record is the WHOLE input record with the four bytes of its time replaced (pass-through: not even
+ *   those), out of place as in place: an AdderEvent's pad, and in an 11-byte record with c = None (tag byte 0: d at
+ *   byte 5, t at bytes 6..9) the unused byte 10, are the input's.
  *   T is kept in 64 bits, so the round-up itself never overflows; the NEXT event of that unit is the bad one.
  *
  * INFO.  adder_stream_info_* fold a batch into the handle's (min, max) exactly as main.rs:74-121 does event by event
@@ -80,6 +83,9 @@ int adder_stream_parse_header(const uint8_t *buf, size_t len, AdderStreamParams 
 size_t adder_stream_migrated_header(const uint8_t *in_header, size_t len, uint32_t time_mode, uint8_t *out,
                                     size_t cap);
 
+/* ADDER_E_BAD_PARAMS (before any device is touched) for parameters out of range, among them a plane whose
+ * width * height * channels + 1 -- the units and the key that sorts bad and EOF records behind them -- does not fit
+ * in 32 bits (65535 x 65535 x 3 is such a plane; every one-channel plane fits). */
 int adder_stream_create(const AdderStreamParams *p, AdderStream **out);
 void adder_stream_destroy(AdderStream *s);
 /* Forgets every unit's time (migration and info) and the (min, max) of the fold. */

@@ -90,3 +90,53 @@ def write_adder(meta, events, close=True):
     if close:
         out += EOF
     return out
+
+
+# ---- tag-aware records (tests/stream_edge_cases.py) ---------------------------------------------------------------
+# An 11-byte record is x, y, Option<u8> c, d, t as bincode lays them out, read back with a fixed 11-byte read
+# (raw/stream.rs:177-201): tag 1 = Some(c): c at byte 5, d at 6, t at 7..10; tag 0 = None: d at byte 5, t at 6..9 and
+# byte 10 belongs to nothing (`spare`, carried); a tag above 1 does not decode and ends the stream like the EOF
+# record (x = y = 0xFFFF).  9-byte records have no tag; their c is None.
+
+def decode_records(body, channels):
+    """-> (events[EVENT_DTYPE] of EVERY whole record, tag u8[n], spare u8[n], end): c = 0xFF for tag 0 and for 9-byte
+    records; `end` is the index of the first record that ends the stream, or n.  Records from `end` on are decoded by
+    their tag's layout all the same (tag > 1: as None) so that a test can say what lay behind the end."""
+    rb = 9 if channels == 1 else 11
+    n = len(body) // rb
+    b = np.frombuffer(bytes(body[: n * rb]), np.uint8).reshape(n, rb).astype(np.uint32)
+    ev = np.zeros(n, EVENT_DTYPE)
+    ev["x"], ev["y"] = (b[:, 0] << 8) | b[:, 1], (b[:, 2] << 8) | b[:, 3]
+    tag, spare = np.ones(n, np.uint8), np.zeros(n, np.uint8)
+    if channels == 1:
+        ev["c"], ev["d"], tb = 0xFF, b[:, 4], b[:, 5:9]
+        ends = (ev["x"] == 0xFFFF) & (ev["y"] == 0xFFFF)
+    else:
+        tag = b[:, 4].astype(np.uint8)
+        some = tag == 1
+        ev["c"] = np.where(some, b[:, 5], 0xFF)
+        ev["d"] = np.where(some, b[:, 6], b[:, 5])
+        tb = np.where(some[:, None], b[:, 7:11], b[:, 6:10])
+        spare = np.where(some, 0, b[:, 10]).astype(np.uint8)
+        ends = (tag > 1) | ((ev["x"] == 0xFFFF) & (ev["y"] == 0xFFFF))
+    ev["t"] = (tb[:, 0] << 24) | (tb[:, 1] << 16) | (tb[:, 2] << 8) | tb[:, 3]
+    hit = np.flatnonzero(ends)
+    return ev, tag, spare, int(hit[0]) if len(hit) else n
+
+
+def encode_records(events, channels, tag=None, spare=None):
+    """The inverse of decode_records on records of tag 0 and 1.  tag None: Some(c), except None where c == 0xFF."""
+    n = len(events)
+    be = lambda v, k: [((v.astype(np.uint32) >> s) & 0xFF).astype(np.uint8) for s in range(8 * k - 8, -8, -8)]
+    cols = be(events["x"], 2) + be(events["y"], 2)
+    d, t = events["d"].astype(np.uint8), be(events["t"], 4)
+    if channels == 1:
+        cols += [d] + t
+    else:
+        tag = np.where(events["c"] == 0xFF, 0, 1).astype(np.uint8) if tag is None else np.asarray(tag, np.uint8)
+        spare = np.zeros(n, np.uint8) if spare is None else np.asarray(spare, np.uint8)
+        assert np.all(tag <= 1) and np.all(events["c"][tag == 0] == 0xFF)
+        some = tag == 1
+        cols += [tag, np.where(some, events["c"], d), np.where(some, d, t[0]), np.where(some, t[0], t[1]),
+                 np.where(some, t[1], t[2]), np.where(some, t[2], t[3]), np.where(some, t[3], spare)]
+    return np.stack(cols, 1).tobytes() if n else b""

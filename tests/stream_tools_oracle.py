@@ -91,9 +91,18 @@ def event_to_intensity(d, t):
     return p if t == 0 else p / float(t)
 
 
+FOLD_ARMS = ("ignored", "lower", "replace_by_128", "replace_by_inf", "to_zero", "sticky", "offered_and_raises",
+             "offered_and_does_not")
+
+
 class Info:
-    def __init__(self, meta):
-        self.meta = meta
+    """census: an optional list; run() appends the arm (one of FOLD_ARMS) that each folded event took.  ignored:
+    D_EMPTY; lower: a < min, min = a; replace_by_128 / replace_by_inf: d == 128 sets min = 1 / t (t > 0 / t == 0);
+    to_zero: d in 129..=254 sets min = 0.0; sticky: d >= 128 met min == 0.0 and moved nothing; offered_and_raises /
+    offered_and_does_not: a >= min, offered to max."""
+
+    def __init__(self, meta, census=None):
+        self.meta, self.census = meta, census
         self.absolute = meta["version"] >= 2 and meta["time_mode"] == ABSOLUTE_T
         self.last_t = {}
         self.min, self.max, self.count = F64_MAX, 0.0, 0
@@ -114,16 +123,23 @@ class Info:
                 t -= last
             a = event_to_intensity(d, t)
             if d == D_EMPTY:
-                pass
+                arm = "ignored"
             elif math.isinf(a):
-                pass  # unreachable: no intensity is infinite
+                arm = None  # unreachable: no intensity is infinite
             elif a < self.min:
                 if d == D_ZERO_INTEGRATION:
                     self.min = 1.0 / t if t != 0 else math.inf
+                    arm = "replace_by_128" if t != 0 else "replace_by_inf"
                 else:
                     self.min = a
+                    arm = "to_zero" if d > D_ZERO_INTEGRATION else "lower"
             elif a > self.max:
                 self.max = a
+                arm = "offered_and_raises"
+            else:
+                arm = "sticky" if d >= D_ZERO_INTEGRATION else "offered_and_does_not"
+            if self.census is not None:
+                self.census.append(arm)
             self.count += 1
         return None
 

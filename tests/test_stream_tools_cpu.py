@@ -336,6 +336,13 @@ def test_create_refuses_bad_parameters():
         p = T.AdderStreamParams(**dict(base, **kw))
         assert L.adder_stream_create(C.byref(p), C.byref(h)) == -1 and not h.value
         assert L.adder_stream_last_error(None)
+    # width * height * channels + 1 (the sentinel key) in 64 bits: 65535 * 65535 * 3 wraps to 4 294 574 083 units in 32
+    # bits, 37838 * 37838 * 3 to 175 436 -- a plausible plane; both are refused before a device is looked for
+    for w, hh in ((65535, 65535), (37838, 37838), (65535, 21846)):
+        assert w * hh * 3 + 1 > 0xFFFFFFFF
+        p = T.AdderStreamParams(**dict(base, width=w, height=hh, channels=3))
+        assert L.adder_stream_create(C.byref(p), C.byref(h)) == -1 and not h.value
+        assert f"plane {w}x{hh}x3".encode() in L.adder_stream_last_error(None)
 
 
 def build_example(tmp_path):
