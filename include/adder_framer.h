@@ -18,7 +18,8 @@
  * switch: the reference stores the mode (driver.rs:270, 383) and never reads it, both modes ingest alike.
  * Frame element types: u8, and u16 / u32 (<u16 / u32 as FrameValue>, scale_intensity.rs:111-209) whose frames are popped
  * as the big-endian bincode bytes the reference's writers produce (driver.rs:279,395-398,944).  FrameSequence<u64> cannot
- * be instantiated in the reference (its methods need T: Into<f64>).  Not built: EventCoordless frames, buffer_limit.
+ * be instantiated in the reference (its methods need T: Into<f64>).  Not built: EventCoordless frames.  buffer_limit is
+ * the adder-viz player's (include/adder_viz_player.h), whose frames depend on when they are popped; this ABI has none.
  *
  * Feature detection while framing (FramerBuilder::detect_features / Framer::detect_features /
  * FrameSequence::pop_features / ::get_running_intensities, driver.rs:48, 140-144, 172, 252-257, 271-275, 401-403,

@@ -1,0 +1,159 @@
+/* adder_viz_player.h -- C-ABI of the adder-viz player (libadder_hip.so): a FrameSequence<u8> with one row per chunk
+ * and a buffer limit, popped the way the reference's interactive player pops it.
+ *
+ * The reference: adder-viz/src/player/adder.rs:319-440 (`consume`) over adder-codec-rs/src/framer/driver.rs:437-562
+ * (ingest_event), 632-677 (flush_frame_buffer), 828-843 (is_frame_0_filled), 878-925 (pop_next_frame), 984-1133
+ * (ingest_event_for_chunk).  The framer is FramerBuilder::new(plane, 1) -- every row is its own chunk --
+ * INSTANTANEOUS, Some(fps), buffer_limit = Some(60) by default.  It sits between the exact framer (adder_framer.h,
+ * which waits for the slowest pixel) and the latest-event player (adder_player.h, no frame queue): exact frames while
+ * every pixel keeps up, a forced, partly empty frame once some pixel runs more than buffer_limit frames ahead.  An
+ * event that arrives after its frame was popped is dropped for that frame, so WHEN frames are popped decides what they
+ * hold: the pop schedule below is reproduced, not sidestepped.  Restated, not fixed.
+ *
+ * Per event.  The per-unit step is the framer's (csrc/adder_framer.hpp, framer_step): the clock and its round-up for
+ * framed cameras, the fill range (from, to], the value (D_EMPTY repeats the last intensity), every view arm for u8.
+ * An AbsoluteT event from the unit's past (prev_ts >= t) changes nothing and takes no part in anything below.  Every
+ * other event is "checked": it has a global stream index i (counted from the context's creation), a row r_i, and
+ * L_i, the unit's last_filled after the event.
+ *
+ * The pop schedule.  W = frames_written, limit = the buffer limit, s = the index of the first event ingested while
+ * frames_written == W.
+ *   Row state.  A row's chunk_filled_tracker entry always equals "frame W of this row is complete or forced"; only the
+ *     row's own events and pops change it.
+ *   nat_r(W): the index of the event that gives frame W of row r its last missing unit; -inf when the row is complete
+ *     before s, +inf while a unit is missing.  An event that covers W always arrives in time to count, because W has
+ *     not been popped.
+ *   forced_r(W, s): the first checked event i >= s of row r with L_i > W + limit; +inf without a limit.  An event from
+ *     before s never forces: the forcing sets filled_count of the then-current frame 0 only.
+ *   End of the period.  E_W = max over rows of min(nat_r(W), forced_r(W, s)).  ingest_event returns true at event E_W
+ *     and at no earlier event of the period.  While E_W is +inf the period stays open across calls.
+ *   The pops at E_W.  Frame W is popped.  Then, with M the largest L of any event <= E_W since creation, W <- W + 1 and
+ *     the pop repeats while (a) limit is set and max(M, W) - W + 1 > limit -- the `chunk.len() > buffer_limit` clause
+ *     of is_frame_0_filled: a row's deque length is max(maxL_r, W) - W + 1 -- or (b) every row's frame W is complete
+ *     by events <= E_W.
+ *   The next period begins at s = E_W + 1.
+ *   Content.  In the frame j popped after event E, unit u is Some(v) if the one event of u whose fill range contains j
+ *     has index <= E; v is the unit's last intensity after that event.  Otherwise u is None: the event was late and is
+ *     dropped for j, or no event covered j.
+ *   running_frame: zero at creation; for each popped frame Some overwrites the unit, None keeps it (adder.rs:342-356).
+ *
+ * The end of the stream, adder_viz_player_finish: the Err arm of `consume`, where flush_frame_buffer and the consume
+ * recursion alternate.  While M > W: the Nones of frame W are filled with each unit's current last_frame_intensity
+ * (the unit's latest value, even one from a later frame: the reference's quirk, reproduced), frame W is popped, then
+ * the pops repeat as above with E = the last event of the stream; frames popped by that repetition keep their Nones.
+ * Frame M is never shown.  A context that was finished takes no more events.
+ *
+ * OURS, stated as ours:
+ *   - limit == 0 is refused (create, set_buffer_limit): the reference's `while is_frame_0_filled()` never ends there,
+ *     a deque always holds at least one frame.
+ *   - no limit (has_buffer_limit = 0) is allowed: the exact framer's frames, popped at the player's positions.
+ *   - pops happen right after the event that completed the period (nothing lies between that event and the next
+ *     `consume`), so any split of a stream into calls gives the same frames; empty calls are allowed.
+ *   - adder_viz_player_set_buffer_limit between calls is adaptive_state_update: the `while` loop of adder.rs:339 runs
+ *     at the start of the next call (or finish) with the new limit.  Without it a call opens with no such loop (the
+ *     reference runs it only after a `consume` returned, and those pops were made right after that event).
+ *   - an event outside the plane at batch index b: the batch commits exactly as if it had ended before b, b is
+ *     reported in *bad_index and the status is ADDER_VIZ_PLAYER_E_BAD_EVENT (the reference skips a row past the plane
+ *     and indexes out of bounds otherwise).
+ *   - frames that do not fit: ADDER_E_OUT_CAPACITY with the needed count in *n_frames, nothing changes.
+ *   - a unit that runs ring_frames or more frames ahead of frames_written: ADDER_E_OUT_CAPACITY with *n_frames = 0 and
+ *     the framer's message (raise ring_frames); nothing changes.
+ *   - wire input stops at an EOF record (x == y == 0xFFFF) or an undecodable record: *n_consumed = the records before
+ *     it; the caller then calls finish.
+ *   - not built: detect_features with a buffer limit (pop_features' deque bookkeeping reads frames_written at every
+ *     event), the overlay crosses of adder.rs:359-388, u16 / u32 frames, compressed input, changing the view
+ *     mid-stream.
+ *
+ * Frames are [n][height][width][channels] u8 in one of two forms:
+ *   ADDER_VIZ_FRAME_POPPED   the popped frame with None as 0: the bytes of the reference's write_frame_bytes;
+ *   ADDER_VIZ_FRAME_RUNNING  the player's running_frame after the frame was applied.
+ * pop_index (host memory, optional, room for frame_cap entries) receives P_j for each frame: the global index of the
+ * event after which it was popped (-1: before the first event). */
+#ifndef ADDER_VIZ_PLAYER_H
+#define ADDER_VIZ_PLAYER_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "adder_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define ADDER_VIZ_PLAYER_ABI_VERSION 1u
+#define ADDER_VIZ_PLAYER_E_BAD_EVENT (-16) /* = ADDER_PLAYER_E_BAD_EVENT */
+#define ADDER_VIZ_PLAYER_NO_BAD_EVENT UINT64_MAX
+
+enum { ADDER_VIZ_FRAME_POPPED = 0, ADDER_VIZ_FRAME_RUNNING = 1 };
+
+typedef struct AdderVizPlayerParams {
+    uint32_t abi_version;   /* = ADDER_VIZ_PLAYER_ABI_VERSION */
+    uint16_t width, height;
+    uint8_t channels;       /* 1 or 3 */
+    uint8_t codec_version;  /* AbsoluteT handling needs >= 2, the round-up >= 1 (driver.rs:1001, 1093) */
+    uint8_t time_mode;      /* ADDER_TIME_* */
+    uint8_t has_buffer_limit; /* 0: None */
+    uint32_t buffer_limit;  /* > 0 when has_buffer_limit (adder-viz's default: 60) */
+    uint32_t tps, ref_interval, delta_t_max;
+    float output_fps;       /* Some(fps): tpf = (tps as f32 / fps) as u32; <= 0: None, tpf = ref_interval */
+    uint32_t source_camera; /* SourceCamera discriminant; 0..5 = framed */
+    uint32_t ring_frames;   /* pending frames kept on the device; 0 = delta_t_max / tpf + 80 */
+    int32_t device_id;
+    uint8_t view_mode;      /* ADDER_VIEW_* (adder_framer.h): 0 Intensity, 1 D, 2 DeltaT, 3 SAE */
+    uint8_t source_type;    /* 0 U8, 1 U16, 2 U32, 3 U64 (Intensity view) */
+    uint16_t reserved0;
+    float practical_d_max;  /* D view, computed by the caller as for adder_framer.h */
+} AdderVizPlayerParams;
+
+typedef struct AdderVizPlayer AdderVizPlayer;
+
+int adder_viz_player_create(const AdderVizPlayerParams *p, AdderVizPlayer **out);
+void adder_viz_player_destroy(AdderVizPlayer *pl);
+/* Back to the start of a stream: the state of a fresh context, the buffer limit as it stands. */
+int adder_viz_player_reset(AdderVizPlayer *pl);
+/* Describes the last failure of `pl` (or of the last failed create when pl is null). */
+const char *adder_viz_player_last_error(const AdderVizPlayer *pl);
+uint32_t adder_viz_player_tpf(const AdderVizPlayer *pl);
+int64_t adder_viz_player_frames_written(const AdderVizPlayer *pl);
+/* has = 0: None.  Takes effect at the start of the next call. */
+int adder_viz_player_set_buffer_limit(AdderVizPlayer *pl, int has, uint32_t limit);
+
+/* n AdderEvents in stream order (device memory).  The frames popped go to d_frames[0 .. *n_frames) in `form`;
+ * frame_cap counts frames.  *bad_index = the index of the bad event within this batch, or
+ * ADDER_VIZ_PLAYER_NO_BAD_EVENT.  Waits for `stream`. */
+int adder_viz_player_ingest_device(AdderVizPlayer *pl, const AdderEvent *d_events, uint64_t n, int form,
+                                   uint8_t *d_frames, uint64_t frame_cap, uint64_t *n_frames, int64_t *pop_index,
+                                   uint64_t *bad_index, void *stream);
+/* The same for n_records raw wire records (the 9 / 11-byte big-endian body of a .adder file). */
+int adder_viz_player_ingest_wire_device(AdderVizPlayer *pl, const uint8_t *d_wire, uint64_t n_records, int form,
+                                        uint8_t *d_frames, uint64_t frame_cap, uint64_t *n_frames, int64_t *pop_index,
+                                        uint64_t *bad_index, uint64_t *n_consumed, void *stream);
+/* The end of the stream (device memory). */
+int adder_viz_player_finish_device(AdderVizPlayer *pl, int form, uint8_t *d_frames, uint64_t frame_cap,
+                                   uint64_t *n_frames, int64_t *pop_index, void *stream);
+/* Host-pointer forms: copy in, run on the device, copy the frames out. */
+int adder_viz_player_ingest(AdderVizPlayer *pl, const AdderEvent *events, uint64_t n, int form, uint8_t *frames,
+                            uint64_t frame_cap, uint64_t *n_frames, int64_t *pop_index, uint64_t *bad_index);
+int adder_viz_player_ingest_wire(AdderVizPlayer *pl, const uint8_t *wire, uint64_t n_records, int form,
+                                 uint8_t *frames, uint64_t frame_cap, uint64_t *n_frames, int64_t *pop_index,
+                                 uint64_t *bad_index, uint64_t *n_consumed);
+int adder_viz_player_finish(AdderVizPlayer *pl, int form, uint8_t *frames, uint64_t frame_cap, uint64_t *n_frames,
+                            int64_t *pop_index);
+/* The running_frame as it stands (host memory). */
+int adder_viz_player_running_frame(AdderVizPlayer *pl, uint8_t *frame);
+
+/* The pop schedule on the host, for self-tests: the arithmetic the schedule kernel runs (coverage counts per row and
+ * pending frame, forced events by a search in a row-ordered prefix maximum, the period loop), on one whole stream fed
+ * to a fresh context in one call.  Per event i of n: row[i]; the fill range (from[i], to[i]] (from == to: none);
+ * L[i] = last_filled after the event, or -1 for an event that is not checked.  `finish` != 0 appends the end of the
+ * stream.  pop_index[k] = P of the k-th popped frame, flushed[k] = 1 when finish filled its Nones.  Returns the number
+ * of popped frames, or -1 when it exceeds `cap` or an argument is out of range. */
+int64_t adder_viz_schedule_host(const int32_t *row, const int32_t *from, const int32_t *to, const int32_t *L,
+                                uint64_t n, uint32_t rows, uint32_t row_units, int has_limit, uint32_t limit,
+                                int finish, int64_t *pop_index, uint8_t *flushed, uint64_t cap);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* ADDER_VIZ_PLAYER_H */
