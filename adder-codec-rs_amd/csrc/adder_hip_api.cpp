@@ -47,8 +47,8 @@ struct AdderHipCtx {
     bool continuous = false;
     float *cn_integ = nullptr, *cn_dt = nullptr, *cn_bdt = nullptr;
     uint32_t *cn_meta = nullptr;
-    uint8_t *state_slab = nullptr;  // hdr, lastf, status, integ0, dt0, bdt0 live in here
-    size_t reset_bytes = 0;         // hdr .. status: one memset per reset
+    uint8_t *state_slab = nullptr;  // hdr, lastf, status + d_run_max, integ0, dt0, bdt0 live in here
+    size_t reset_bytes = 0;         // hdr .. the status block: one memset per reset
     size_t slab_bytes = 0;
     uint8_t *running = nullptr;       // the context's own rows, inside running_base
     uint8_t *running_base = nullptr;  // kFeatureHalo rows of the band above + the own rows (n_pad) + kFeatureHalo rows below
@@ -65,6 +65,12 @@ struct AdderHipCtx {
         float *cn_integ = nullptr, *cn_dt = nullptr, *cn_bdt = nullptr;
         uint32_t *cn_meta = nullptr;
         bool valid = false, deep = false;
+        // "lean2": only the header and delta_t planes of `slab` are valid, and the batch's first adder_lp_kernel launch
+        // writes them (BatchArgs::snap_hdr / snap_dt) -- no copy is queued in front of the batch.  In the lean-runs regime
+        // the other two level-0 planes follow from those two (lr_pack of lr_unpack: adder_lp_restore_kernel), and the
+        // packed kernel writes nothing else: not last_fired_t, not a deep level, no per-unit c_thresh or feature plane.
+        bool lean2 = false;
+        float time_spanned = 0.0f;  // of the batch (lean2: the restore kernel's time step)
         float running_t = 0.0f;
         uint8_t c_thresh = 0, c_counter = 0;
         uint64_t frames_done = 0, run_bound = 0;
@@ -122,7 +128,7 @@ struct AdderHipCtx {
     uint64_t run_bound = 0, pending_end_frames = 0;
     bool pending_reports = false;
     hipEvent_t null_join = nullptr;  // stream == NULL: the batch is ordered behind the legacy default stream (join_null_stream)
-    uint32_t *d_run_max = nullptr;
+    uint32_t *d_run_max = nullptr;   // (in the status block of state_slab, a cache line behind the status word: cleared by the reset's one fill)
     uint32_t *wtot_ring = nullptr;   // [slots][num_waves]
     uint32_t *wpref_ring = nullptr;  // [slots][num_waves]
     uint32_t *ftot_ring = nullptr;   // [slots]
@@ -368,7 +374,6 @@ static void free_ctx(AdderHipCtx *c) {
     if (c->d_rec_total) (void)hipFree(c->d_rec_total);
     if (c->d_side_words) (void)hipFree(c->d_side_words);
     if (c->d_rr_tab) (void)hipFree(c->d_rr_tab);
-    if (c->d_run_max) (void)hipFree(c->d_run_max);
     if (c->d_lr_tab) (void)hipFree(c->d_lr_tab);
     if (c->d_band_desc) (void)hipFree(c->d_band_desc);
     if (c->h_band_desc) (void)hipHostFree(c->h_band_desc);
@@ -484,6 +489,7 @@ static void base_args(const AdderHipCtx *c, FrameArgs *a) {
     a->row_begin = c->p.row_begin;
 }
 
+constexpr size_t kStatusBlockBytes = 256;  // the status word (+0) and d_run_max (+128) between the planes of state_slab
 static size_t halo_bytes(const AdderHipCtx *c) { return (size_t)kFeatureHalo * c->p.width * c->p.channels; }
 static int alloc_running(AdderHipCtx *c, hipStream_t s) {
     if (c->running) return ADDER_OK;
@@ -509,9 +515,9 @@ static int init_state(AdderHipCtx *c) {
         HIPCHK(c, hipMemsetAsync(c->cn_bdt, 0, cnt * sizeof(float), c->stream));
         HIPCHK(c, hipMemsetAsync(c->cn_meta, 0, cnt * sizeof(uint32_t), c->stream));
         HIPCHK(c, hipMemsetAsync(c->lastf, 0, c->n_pad * sizeof(float), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->status, 0, sizeof(uint32_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->status, 0, kStatusBlockBytes, c->stream));
     } else {
-        HIPCHK(c, hipMemsetAsync(c->state_slab, 0, c->reset_bytes, c->stream));  // hdr, last_fired_t, status
+        HIPCHK(c, hipMemsetAsync(c->state_slab, 0, c->reset_bytes, c->stream));  // hdr, last_fired_t, status, d_run_max
     }
     if (c->running_base) HIPCHK(c, hipMemsetAsync(c->running_base, 0, c->n_pad + 2 * halo_bytes(c), c->stream));
     c->band_frame_pending = false;
@@ -523,9 +529,6 @@ static int init_state(AdderHipCtx *c) {
     c->cr_time = 0.0f;
     c->run_bound = 0;
     c->pending_reports = false;
-#ifndef ADDER_DBG_NO_RUNMAX_RESET
-    if (c->d_run_max) HIPCHK(c, hipMemsetAsync(c->d_run_max, 0, sizeof(uint32_t), c->stream));
-#endif
     c->dtm_max_seen = p.delta_t_max;
     c->perpx = false;
     c->sparse_mode = false;
@@ -652,15 +655,18 @@ extern "C" int adder_hip_create(const AdderHipParams *params, AdderHipCtx **out)
             // to the allocator (measured: the same build ran at 1.82 or 1.97 ms per step from context to context).
             const size_t skew = 4352;
             const size_t plane = (c->n_pad * sizeof(uint32_t) + 255) & ~(size_t)255;
-            c->slab_bytes = 5 * (plane + skew) + 256;
+            c->slab_bytes = 5 * (plane + skew) + kStatusBlockBytes;
             HIPCHK(c, dalloc(&c->state_slab, c->slab_bytes));
-            // header plane, last_fired_t plane and the status word first: what a reset clears is one range
+            // header plane, last_fired_t plane and the status block first: what a reset clears is one range.  The block
+            // holds every word a reset zeroes: the status word and, a cache line on, the integer-state kernels' run report
+            // (adder_publish_kernel clears that one behind every batch as well)
             uint8_t *q = c->state_slab;
             c->hdr = reinterpret_cast<uint32_t *>(q);
             c->lastf = reinterpret_cast<float *>(q + 1 * (plane + skew));
             c->status = reinterpret_cast<uint32_t *>(q + 2 * (plane + skew));
-            c->reset_bytes = 2 * (plane + skew) + 256;
-            q += 256;
+            c->d_run_max = c->status + 32;
+            c->reset_bytes = 2 * (plane + skew) + kStatusBlockBytes;
+            q += kStatusBlockBytes;
             c->integ0 = reinterpret_cast<float *>(q + 2 * (plane + skew));
             c->dt0 = reinterpret_cast<float *>(q + 3 * (plane + skew));
             c->bdt0 = reinterpret_cast<float *>(q + 4 * (plane + skew));
@@ -1122,6 +1128,7 @@ static int launch_frame_loop(AdderHipCtx *c, uint32_t num_frames, uint32_t varia
     // to their unit, so the lane's own program order keeps them consistent across frames.
     const uint32_t depth = launch_depth(c);
     const Lean1wArgs wide = lean1w_args(c);
+    const bool keep_undo = c->snap.valid && c->snap.lean2;  // the first launch keeps the batch's undo copy (get_graph keys on it)
     // With a second stream the expansion of chunk k runs beside the frame kernel of chunk k+1.  The frame kernel is
     // bound by instruction issue, the expansion by memory, and two grids that each fill the chip would simply run one
     // after the other (measured: the scan queued behind the resident frame kernel for a whole kernel time): both are
@@ -1140,7 +1147,8 @@ static int launch_frame_loop(AdderHipCtx *c, uint32_t num_frames, uint32_t varia
         for (uint32_t f = f0; f < f0 + nf; f += depth) {
             const uint32_t nb = std::min(depth, f0 + nf - f);
             if (timing && !per_chunk) HIPCHK(c, hipEventRecord(c->launch_events[2 * c->timed_pairs], s));
-            HIPCHK(c, adder_launch_frame(c->d_batch, f, nb, variant | variant_lazy_state_bit(variant, f + nb < num_frames, c->running_enabled), c->num_waves, lean_cap, s, &wide));
+            HIPCHK(c, adder_launch_frame(c->d_batch, f, nb, variant | variant_lazy_state_bit(variant, f + nb < num_frames, c->running_enabled) | variant_keep_undo_bit(variant, f == 0u, keep_undo),
+                                         c->num_waves, lean_cap, s, &wide));
             if (timing) {  // the pair brackets the frame kernel (K1) only
                 if (!per_chunk) {
                     HIPCHK(c, hipEventRecord(c->launch_events[2 * c->timed_pairs + 1], s));
@@ -1211,8 +1219,10 @@ static int get_graph(AdderHipCtx *c, uint32_t num_frames, uint32_t variant, hipG
     // everything the captured launch sequence depends on
     // (running_enabled decides the launches' lazy bits, variant_lazy_state_bit)
     // (graph_slot: a frame slot of the per-frame ring has its own description, so its own graphs)
+    // (the first launch's kVarKeepUndo: a batch that keeps a two-plane undo copy and one that needs none are two sequences)
     // (bits: frames 0-23, variant 24-39, launch depth 40-47, running 48, frame slot 49-)
-    const uint64_t key = (uint64_t)(num_frames & 0xffffffu) | ((uint64_t)(variant & kVarKeyMask) << 24) | ((uint64_t)(launch_depth(c) & 0xffu) << 40) |
+    const uint32_t key_variant = variant | variant_keep_undo_bit(variant, true, c->snap.valid && c->snap.lean2);
+    const uint64_t key = (uint64_t)(num_frames & 0xffffffu) | ((uint64_t)(key_variant & kVarKeyMask) << 24) | ((uint64_t)(launch_depth(c) & 0xffu) << 40) |
                          ((uint64_t)(c->running_enabled ? 1u : 0u) << 48) | ((uint64_t)c->graph_slot << 49);
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
@@ -1304,8 +1314,20 @@ static hipError_t snap_copy(T **dst, const T *src, size_t count, hipStream_t s) 
     }
     return hipMemcpyAsync(*dst, src, count * sizeof(T), hipMemcpyDeviceToDevice, s);
 }
+// the host's side of the undo copy
+static void snapshot_scalars(AdderHipCtx *c) {
+    AdderHipCtx::Snapshot &n = c->snap;
+    n.running_t = c->running_t;
+    n.c_thresh = c->c_thresh;
+    n.c_counter = c->c_counter;
+    n.frames_done = c->frames_done;
+    n.run_bound = c->run_bound;
+    n.generic_sticky = c->generic_sticky;
+    n.valid = true;
+}
 static int take_snapshot(AdderHipCtx *c, bool deep, hipStream_t s) {
     AdderHipCtx::Snapshot &n = c->snap;
+    n.lean2 = false;
     HIPCHK(c, snap_copy(&n.slab, c->state_slab, c->slab_bytes, s));  // the five level-0 planes + status, one copy
     if (c->continuous) {
         const size_t cnt = c->n_pad * (c->max_depth + 1u);
@@ -1332,19 +1354,49 @@ static int take_snapshot(AdderHipCtx *c, bool deep, hipStream_t s) {
     if (c->fset) HIPCHK(c, snap_copy(&n.fset, c->fset, (size_t)c->rows * c->p.width, s));
     n.has_running = c->running != nullptr;
     if (c->running) HIPCHK(c, snap_copy(&n.running, c->running, c->n_pad, s));
-    n.running_t = c->running_t;
-    n.c_thresh = c->c_thresh;
-    n.c_counter = c->c_counter;
-    n.frames_done = c->frames_done;
-    n.run_bound = c->run_bound;
-    n.generic_sticky = c->generic_sticky;
-    n.valid = true;
+    snapshot_scalars(c);
+    return ADDER_OK;
+}
+// Can the batch keep its own undo copy (Snapshot::lean2)?  Its plan starts with adder_lp_kernel, and the context holds none
+// of the planes take_snapshot copies besides the slab: no per-unit c_thresh, no feature set, no running intensities, no
+// Continuous arena (the packed kernel's regime has no deep level to keep).
+static bool lean2_possible(const AdderHipCtx *c, uint32_t variant) {
+    return variant_frame_kernel(variant) == ADDER_KERNEL_LEAN_RUNS_PACKED && !c->continuous && !c->perpx && !c->fset && !c->running;
+}
+// ... then nothing is queued: the copy's planes only have to exist (laid out like state_slab; its header and delta_t
+// planes are the ones written, snap_plane)
+static int take_snapshot_lean2(AdderHipCtx *c, float time_spanned) {
+    AdderHipCtx::Snapshot &n = c->snap;
+    if (!n.slab) HIPCHK(c, dalloc(&n.slab, c->slab_bytes));
+    n.lean2 = true;
+    n.time_spanned = time_spanned;
+    n.deep = n.perpx = n.has_running = false;
+    snapshot_scalars(c);
+    return ADDER_OK;
+}
+// the undo copy's counterpart of a plane of state_slab
+template <class T>
+static T *snap_plane(const AdderHipCtx *c, const T *plane) {
+    return reinterpret_cast<T *>(c->snap.slab + (reinterpret_cast<const uint8_t *>(plane) - c->state_slab));
+}
+// Rolls a lean2 copy back: the two planes the batch's first launch kept -> the four resident planes (adder_lp_restore_kernel).
+// last_fired_t is as it was (adder_lp_kernel does not touch it in DeltaT); the run report was cleared behind the batch.
+// (A batch whose first launch raises kStatusLeanRuns never gets here -- only a pure capacity status is rolled back; the
+// planes it refused are the very planes it copied, untouched.)
+static int restore_snapshot_lean2(AdderHipCtx *c, hipStream_t s) {
+    HIPCHK(c, adder_launch_lp_restore(snap_plane(c, c->hdr), snap_plane(c, c->dt0), c->hdr, c->integ0, c->dt0, c->bdt0,
+                                      (uint32_t)c->n_pad, c->snap.time_spanned, s));
     return ADDER_OK;
 }
 static int restore_snapshot(AdderHipCtx *c, hipStream_t s) {
     AdderHipCtx::Snapshot &n = c->snap;
-    HIPCHK(c, hipMemcpyAsync(c->state_slab, n.slab, c->slab_bytes, hipMemcpyDeviceToDevice, s));
-    if (c->continuous) {
+    if (n.lean2) {
+        int rc_ = restore_snapshot_lean2(c, s);
+        if (rc_ != ADDER_OK) return rc_;
+    } else {
+        HIPCHK(c, hipMemcpyAsync(c->state_slab, n.slab, c->slab_bytes, hipMemcpyDeviceToDevice, s));
+    }
+    if (!n.lean2 && c->continuous) {
         const size_t cnt = c->n_pad * (c->max_depth + 1u);
         HIPCHK(c, hipMemcpyAsync(c->cn_integ, n.cn_integ, cnt * sizeof(float), hipMemcpyDeviceToDevice, s));
         HIPCHK(c, hipMemcpyAsync(c->cn_dt, n.cn_dt, cnt * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1362,7 +1414,7 @@ static int restore_snapshot(AdderHipCtx *c, hipStream_t s) {
         HIPCHK(c, hipMemcpyAsync(c->cth_px, n.cth_px, c->n_pad, hipMemcpyDeviceToDevice, s));
         HIPCHK(c, hipMemcpyAsync(c->cctr_px, n.cctr_px, c->n_pad, hipMemcpyDeviceToDevice, s));
     }
-    if (c->fset && n.fset) HIPCHK(c, hipMemcpyAsync(c->fset, n.fset, (size_t)c->rows * c->p.width, hipMemcpyDeviceToDevice, s));
+    if (!n.lean2 && c->fset && n.fset) HIPCHK(c, hipMemcpyAsync(c->fset, n.fset, (size_t)c->rows * c->p.width, hipMemcpyDeviceToDevice, s));
     c->perpx = n.perpx;
     if (c->running && n.has_running) HIPCHK(c, hipMemcpyAsync(c->running, n.running, c->n_pad, hipMemcpyDeviceToDevice, s));
     HIPCHK(c, hipMemsetAsync(c->status, 0, sizeof(uint32_t), s));
@@ -1433,10 +1485,6 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
         int rc_ = ensure_lr_tab(c, time_spanned, stream);
         if (rc_ != ADDER_OK) return rc_;
     }
-    if ((lr || rr) && !c->d_run_max) {
-        HIPCHK(c, dalloc(&c->d_run_max, 1));
-        HIPCHK(c, hipMemset(c->d_run_max, 0, sizeof(uint32_t)));  // (once: adder_publish_kernel clears it behind every batch)
-    }
     if (rr && !c->d_rr_tab) {  // (does not depend on the time step: a node's last firing is ceil(2^e / I))
         std::vector<uint8_t> tab(256u * kRrTabRows);
         rr_build_tab(tab.data(), 255.0f);
@@ -1458,7 +1506,7 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
     }
     c->snap.valid = false;
     if (out_cap < worst_case_events_per_frame(in) * num_frames && !c->no_snapshot) {
-        int rc_ = take_snapshot(c, generic, stream);
+        int rc_ = lean2_possible(c, variant) ? take_snapshot_lean2(c, time_spanned) : take_snapshot(c, generic, stream);
         if (rc_ != ADDER_OK) return rc_;
         c->snap.generic_sticky = sticky_before;
     }
@@ -1513,6 +1561,9 @@ static int enqueue_frames(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_
         b.snap_dv_dt = sd ? c->snap.dv_dt : nullptr;
         b.snap_dv_bdt = sd ? c->snap.dv_bdt : nullptr;
         b.snap_dv_bd = sd ? c->snap.dv_bd : nullptr;
+        const bool s2 = c->snap.valid && c->snap.lean2;  // ... of the two planes the packed kernel's state lives in
+        b.snap_hdr = s2 ? snap_plane(c, c->hdr) : nullptr;
+        b.snap_dt = s2 ? snap_plane(c, c->dt0) : nullptr;
     }
     b.run_max = (lr || rr) ? c->d_run_max : nullptr;
     b.view = make_view(c);

@@ -160,6 +160,11 @@ struct BatchArgs {
     // copy of the whole planes moved (max_depth - 1) * 13 bytes per unit and batch, 6 GB for a 4K RGB plane.
     float *snap_dv_integ, *snap_dv_dt, *snap_dv_bdt;
     uint8_t *snap_dv_bd;
+    // The two-plane undo copy of a batch that starts with adder_lp_kernel: in the lean-runs regime a unit's whole state is
+    // a function of its header and delta_t (lr_unpack), so the launch with kVarKeepUndo stores the two values it loaded
+    // here ([n_pad] each) and adder_lp_restore_kernel rebuilds the four resident planes from them (null otherwise)
+    uint32_t *snap_hdr;
+    float *snap_dt;
     // diagnostics (null in normal operation): first start / last end of every kernel of the batch on the 100 MHz
     // constant clock, [kernel kind 0 frame, 1 scan, 2 offsets, 3 expansion][chunk][2]  (tools/timeline_probe.py)
     unsigned long long *timeline;
@@ -290,8 +295,13 @@ hipError_t adder_launch_frame(const adder::BatchArgs *b, uint32_t f, uint32_t nb
                               uint32_t num_waves, uint32_t grid_cap, hipStream_t stream,
                               const adder::Lean1wArgs *wide);  // (host copy of the level-0 planes, or null)
 // the lean-runs step in packed bytes (adder_lp_kernels.hip; kVarPacked): a wave per PAIR of segments
-hipError_t adder_launch_lp(const adder::BatchArgs *b, uint32_t f, uint32_t nb, uint32_t lazy, uint32_t num_waves,
+// (keep_undo: the launch stores the header and delta_t it loads into BatchArgs::snap_hdr / snap_dt -- kVarKeepUndo)
+hipError_t adder_launch_lp(const adder::BatchArgs *b, uint32_t f, uint32_t nb, uint32_t lazy, uint32_t keep_undo, uint32_t num_waves,
                            uint32_t grid_cap, hipStream_t stream);
+// the rollback of a two-plane undo copy: (snap_hdr, snap_dt)[n_pad] -> the four resident planes, as the batch's last
+// adder_lp_kernel launch writes them (lr_pack of lr_unpack); n_pad is a multiple of 4
+hipError_t adder_launch_lp_restore(const uint32_t *snap_hdr, const float *snap_dt, uint32_t *hdr, float *integ0, float *dt0, float *bdt0,
+                                   uint32_t n_pad, float time_spanned, hipStream_t stream);
 // ... and its expansion (adder_lpx_kernel): rec = 9 / 11 (the raw sink's records) or 12 (AdderEvents)
 // (host_b: the host's copy of *b; frames [f0, f0 + nf) lie in ONE chunk of the scratch ring)
 hipError_t adder_launch_lpx(const adder::BatchArgs *b, const adder::BatchArgs *host_b, uint32_t f0, uint32_t nf, uint32_t rec,

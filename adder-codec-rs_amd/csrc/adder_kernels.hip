@@ -3692,7 +3692,7 @@ extern "C" hipError_t adder_launch_frame(const BatchArgs *b, uint32_t f, uint32_
     }
     if (!collapse) return hipErrorInvalidValue;  // the lean step is Collapse-only
     if (kernel == ADDER_KERNEL_LEAN_RUNS_PACKED)  // (adder_lp_kernels.hip): DeltaT batches of events or wire records
-        return adder_launch_lp(b, f, nb, lazy, num_waves, grid_cap, stream);
+        return adder_launch_lp(b, f, nb, lazy, (variant & kVarKeepUndo) ? 1u : 0u, num_waves, grid_cap, stream);
     if (kernel == ADDER_KERNEL_LEAN_RUNS) {  // (DeltaT, constant runs): every launch of the batch, whatever its length
         const uint32_t SR = grid_cap && grid_cap < S ? grid_cap : S;
         if (abs_t) hipLaunchKernelGGL((adder_lr_kernel<true>), dim3(SR), dim3(kBlockThreads), 0, stream, b, f, nb, lazy);

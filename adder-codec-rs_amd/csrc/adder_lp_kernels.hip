@@ -59,7 +59,8 @@ __device__ __forceinline__ uint32_t lp_bcnt(uint32_t x, uint32_t acc) { return (
 
 template <bool FULL>
 __device__ __forceinline__ void lp_frames(const BatchArgs *__restrict__ b, const FrameArgs &a, uint32_t nb, uint32_t pw,
-                                          uint32_t lane, uint8_t *lds_in, uint32_t *lds_tot, uint32_t *rec_lds, bool lazy) {
+                                          uint32_t lane, uint8_t *lds_in, uint32_t *lds_tot, uint32_t *rec_lds, bool lazy,
+                                          bool keep_undo) {
     const float T = a.sc.time_spanned;
     const uint32_t spw = __builtin_amdgcn_readfirstlane(pw);
     const uint32_t sgw = spw * 2u;  // the pair's first segment
@@ -128,6 +129,10 @@ __device__ __forceinline__ void lp_frames(const BatchArgs *__restrict__ b, const
     {
         const uint4 hv = gload_nt<uint4>(a.hdr, u0 * 4u);
         const float4 dv = gload_nt<float4>(a.dt0, u0 * 4u);
+        if (keep_undo) {  // (uniform) the batch's two-plane undo copy: nothing writes a state plane before this launch's last instruction
+            gstore_nt<uint4>(uniform_ptr(b->snap_hdr), u0 * 4u, hv);  // (padding units too: the copy's planes hold n_pad units)
+            gstore_nt<float4>(uniform_ptr(b->snap_dt), u0 * 4u, dv);
+        }
         const uint32_t hdrv[4] = {hv.x, hv.y, hv.z, hv.w};
         const float dtv[4] = {dv.x, dv.y, dv.z, dv.w};
         LrPx p[4];
@@ -343,7 +348,8 @@ __device__ __forceinline__ void lp_frames(const BatchArgs *__restrict__ b, const
 }
 
 __global__ __launch_bounds__(kBlockThreads, ADDER_LP_WAVES_PER_SIMD) void adder_lp_kernel(const BatchArgs *__restrict__ b,
-                                                                                         uint32_t f, uint32_t nb, uint32_t lazy) {
+                                                                                         uint32_t f, uint32_t nb, uint32_t lazy,
+                                                                                         uint32_t keep_undo) {
     const FrameArgs a = frame_args(b, f);
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & (kWave - 1);
@@ -355,8 +361,8 @@ __global__ __launch_bounds__(kBlockThreads, ADDER_LP_WAVES_PER_SIMD) void adder_
     const uint32_t num_pairs = a.num_waves / 2u;  // (num_waves is a multiple of kExpandSegs)
     for (uint32_t pw = blockIdx.x * kWavesPerBlock + tid / kWave; pw < num_pairs; pw += gridDim.x * kWavesPerBlock) {
         const bool full = __builtin_amdgcn_readfirstlane(pw * kLpPairUnits + kLpPairUnits <= a.n_units);
-        if (full) lp_frames<true>(b, a, nb, pw, lane, s_in[tid / kWave], s_tot[tid / kWave], s_rec[tid / kWave], lazy != 0u);
-        else lp_frames<false>(b, a, nb, pw, lane, s_in[tid / kWave], s_tot[tid / kWave], s_rec[tid / kWave], lazy != 0u);
+        if (full) lp_frames<true>(b, a, nb, pw, lane, s_in[tid / kWave], s_tot[tid / kWave], s_rec[tid / kWave], lazy != 0u, keep_undo != 0u);
+        else lp_frames<false>(b, a, nb, pw, lane, s_in[tid / kWave], s_tot[tid / kWave], s_rec[tid / kWave], lazy != 0u, keep_undo != 0u);
     }
     timeline_mark(b, 0u, f, true);
 }
@@ -733,15 +739,73 @@ __global__ __launch_bounds__(kLpxWaves * kWave) void adder_lpx_kernel(const Batc
         lpx_wave<REC>(b, x, f0 + fy, fy, seg0, threadIdx.x & (kWave - 1u), (ADDER_LDS uint8_t *)s_stage[wid], (ADDER_LDS lpx_u32x2 *)s_rec[wid]);
 }
 
+// ------------------------------------------------------------------------------------------
+// The rollback of a two-plane undo copy (BatchArgs::snap_hdr / snap_dt): the state adder_lp_kernel loaded before the batch's
+// first frame, brought to the resident form {header, integration, delta_t, best delta_t} the way the batch's last launch
+// writes it -- lr_pack of lr_unpack -- so that any kernel may follow.  A lane takes four units; last_fired_t and everything
+// else the regime does not write stay as they are.  (The rare path: an event buffer that overflowed.)
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlockThreads) void adder_lp_restore_kernel(const uint32_t *__restrict__ snap_hdr, const float *__restrict__ snap_dt,
+                                                                         uint32_t *__restrict__ hdr, float *__restrict__ integ0,
+                                                                         float *__restrict__ dt0, float *__restrict__ bdt0, uint32_t n_pad, float T) {
+    const uint32_t u0 = (blockIdx.x * kBlockThreads + threadIdx.x) * kLpUnits;
+    if (u0 >= n_pad) return;
+    uint32_t hv[4] = {0u, 0u, 0u, 0u};
+    float dv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const bool whole = u0 + kLpUnits <= n_pad;
+    if (whole) {
+        const uint4 h4 = gload<uint4>(snap_hdr, u0 * 4u);
+        const float4 d4 = gload<float4>(snap_dt, u0 * 4u);
+        hv[0] = h4.x, hv[1] = h4.y, hv[2] = h4.z, hv[3] = h4.w;
+        dv[0] = d4.x, dv[1] = d4.y, dv[2] = d4.z, dv[3] = d4.w;
+    } else {
+        for (uint32_t j = 0; u0 + j < n_pad; ++j) {
+            hv[j] = gload<uint32_t>(snap_hdr, (u0 + j) * 4u);
+            dv[j] = gload<float>(snap_dt, (u0 + j) * 4u);
+        }
+    }
+    uint32_t ho[4], io[4], dout[4], bo[4];
+#pragma unroll
+    for (uint32_t j = 0; j < kLpUnits; ++j) {
+        bool ok;  // (the batch's first launch has checked the planes it stored: a violation is no capacity status, nothing is rolled back)
+        const LrPx p = lr_unpack<ScalarLanes>(hv[j], dv[j], T, ok);
+        float fi, fd, fb;
+        ho[j] = lr_pack<ScalarLanes>(p, T, fi, fd, fb);
+        io[j] = __float_as_uint(fi);
+        dout[j] = __float_as_uint(fd);
+        bo[j] = __float_as_uint(fb);
+    }
+    if (whole) {
+        gstore<uint4>(hdr, u0 * 4u, make_uint4(ho[0], ho[1], ho[2], ho[3]));
+        gstore<uint4>(integ0, u0 * 4u, make_uint4(io[0], io[1], io[2], io[3]));
+        gstore<uint4>(dt0, u0 * 4u, make_uint4(dout[0], dout[1], dout[2], dout[3]));
+        gstore<uint4>(bdt0, u0 * 4u, make_uint4(bo[0], bo[1], bo[2], bo[3]));
+    } else {
+        for (uint32_t j = 0; u0 + j < n_pad; ++j) {
+            gstore<uint32_t>(hdr, (u0 + j) * 4u, ho[j]);
+            gstore<uint32_t>(integ0, (u0 + j) * 4u, io[j]);
+            gstore<uint32_t>(dt0, (u0 + j) * 4u, dout[j]);
+            gstore<uint32_t>(bdt0, (u0 + j) * 4u, bo[j]);
+        }
+    }
+}
+
 }  // namespace adder
 
 using namespace adder;
-extern "C" hipError_t adder_launch_lp(const BatchArgs *b, uint32_t f, uint32_t nb, uint32_t lazy, uint32_t num_waves,
+extern "C" hipError_t adder_launch_lp_restore(const uint32_t *snap_hdr, const float *snap_dt, uint32_t *hdr, float *integ0, float *dt0,
+                                              float *bdt0, uint32_t n_pad, float time_spanned, hipStream_t stream) {
+    const uint32_t per_block = kBlockThreads * kLpUnits;
+    hipLaunchKernelGGL(adder_lp_restore_kernel, dim3((n_pad + per_block - 1u) / per_block), dim3(kBlockThreads), 0, stream, snap_hdr, snap_dt,
+                       hdr, integ0, dt0, bdt0, n_pad, time_spanned);
+    return hipGetLastError();
+}
+extern "C" hipError_t adder_launch_lp(const BatchArgs *b, uint32_t f, uint32_t nb, uint32_t lazy, uint32_t keep_undo, uint32_t num_waves,
                                       uint32_t grid_cap, hipStream_t stream) {
     const uint32_t pairs = num_waves / 2u;
     uint32_t grid = (pairs + kWavesPerBlock - 1u) / kWavesPerBlock;
     if (grid_cap && grid_cap < grid) grid = grid_cap;
-    hipLaunchKernelGGL(adder_lp_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, b, f, nb, lazy);
+    hipLaunchKernelGGL(adder_lp_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, b, f, nb, lazy, keep_undo);
     return hipGetLastError();
 }
 

@@ -25,6 +25,7 @@ constexpr uint32_t kVarLazyState = 2048u;   // more launches of this batch follo
 constexpr uint32_t kVarPacked = 4096u;      // lean runs in packed bytes (adder_lp_kernel / adder_lpx_kernel)
 constexpr uint32_t kVarPackedRgb = 8192u;   // ... on a three-channel plane (11-byte wire records)
 constexpr uint32_t kVarView = 16384u;       // the side plane shows D, DeltaT or SAE: the kernels' view instantiations
+constexpr uint32_t kVarKeepUndo = 32768u;   // this launch keeps the batch's two-plane undo copy (variant_keep_undo_bit)
 constexpr uint32_t kVarKeyMask = 0xffffu;   // the bits the graph cache key holds
 
 // The frame kernel a variant runs (ADDER_KERNEL_*), in adder_launch_frame's order of precedence.
@@ -53,6 +54,13 @@ inline bool variant_scan_chains(uint32_t v) {
 // 160 us launch were this epilogue.)
 inline uint32_t variant_lazy_state_bit(uint32_t v, bool more_launches, bool running_enabled) {
     return (more_launches && (v & (kVarLeanRuns | kVarRunRecords)) && !running_enabled) ? kVarLazyState : 0u;
+}
+
+// The packed lean-runs kernel loads a unit's whole state -- header and delta_t (lr_unpack) -- before its first frame and
+// writes no state plane until its last: the FIRST launch of a batch that keeps the two-plane undo copy stores what it
+// loaded into the copy's planes (BatchArgs::snap_hdr / snap_dt), and the host queues no copy in front of the batch.
+inline uint32_t variant_keep_undo_bit(uint32_t v, bool first_launch, bool two_plane_undo) {
+    return (first_launch && two_plane_undo && (v & kVarPacked)) ? kVarKeepUndo : 0u;
 }
 
 // Graph instances a batch length tries before it settles (get_graph): a batch of a single chunk has no second branch
