@@ -280,12 +280,46 @@ def load():
             f"{LIB_PATH} not found: build it with `make -C adder-codec-rs_amd` "
             "(hipcc, gfx950).  This path has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    _declare(L, SYMBOLS)
+    _lib = L
+    return L
+
+
+def _declare(L, symbols):
+    for name, (res, args) in symbols.items():
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args
-    _lib = L
+
+
+_bound = set()
+
+
+def bind(symbols):
+    """-> the library (loaded once, by load()), with restype / argtypes set from a tool module's SYMBOLS table
+    (name -> (restype, argtypes)) the first time the table is seen.  Raises if the library lacks one of them."""
+    L = load()
+    if id(symbols) not in _bound:
+        _declare(L, symbols)
+        _bound.add(id(symbols))
     return L
+
+
+class Handle:
+    """close / __del__ of a class that holds a native context in self.h and the library in self.L; DESTROY is the
+    name of the context's destroy function."""
+    DESTROY = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.L, self.DESTROY)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def check_framer(fr, rc):

@@ -58,19 +58,10 @@ SYMBOLS = {
     "adder_dvs_log1p_host": (None, [_vp, _vp, _u64]),
     "adder_dvs_log1p_device": (_i32, [_vp, _vp, _u64, _i32]),
 }
-_lib = None
 
 
 def load():
-    global _lib
-    if _lib is None:
-        L = N.load()
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)  # AttributeError if the library does not export it
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
+    return N.bind(SYMBOLS)
 
 
 def log1p(x):
@@ -127,12 +118,13 @@ def format_text(events):
     return buf.raw[:n]
 
 
-class HipDvs:
+class HipDvs(N.Handle):
     """Per-unit DVS state on one device.  Every convert call continues the stream where the last one stopped.
 
     After a call: .bad_index is the index (within that call's input) of the event that stopped it, or None -- the
     events before it are applied and their output returned, nothing after it is; .consumed is the number of wire
     records before an EOF record (all of them when there is none)."""
+    DESTROY = "adder_dvs_destroy"
 
     def __init__(self, width, height, channels=1, time_mode=N.TIME_DELTA_T, ref_interval=255, source_camera=0,
                  theta=0.01, device_id=0):
@@ -152,17 +144,6 @@ class HipDvs:
     def from_header(cls, buf, theta=0.01, device_id=0):
         meta, _, _ = parse_header(buf)
         return cls(theta=theta, device_id=device_id, **meta)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.adder_dvs_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         self._check(self.L.adder_dvs_reset(self.h))

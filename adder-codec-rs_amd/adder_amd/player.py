@@ -56,19 +56,10 @@ SYMBOLS = {
     "adder_player_schedule_host": (None, [_vp, _u64, _u64, _u64, _vp]),
     "adder_player_frame_length": (_u64, [C.c_uint32, C.c_double]),
 }
-_lib = None
 
 
 def load():
-    global _lib
-    if _lib is None:
-        L = N.load()
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)  # AttributeError if the library does not export it
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
+    return N.bind(SYMBOLS)
 
 
 def parse_header(buf):
@@ -99,7 +90,7 @@ def schedule_host(cur_before, f0, fl):
     return marks
 
 
-class HipPlayer:
+class HipPlayer(N.Handle):
     """The player's state on one device.  Every play call continues the stream where the last one stopped.
 
     After a call: .bad_index is the index (within that call's input) of the event that stopped it, or None -- the
@@ -108,6 +99,7 @@ class HipPlayer:
 
     A call whose frames do not fit max_frames raises AdderHipError(E_OUT_CAPACITY) with .needed = the count, and
     changes nothing."""
+    DESTROY = "adder_player_destroy"
 
     def __init__(self, width, height, channels=1, time_mode=N.TIME_DELTA_T, ref_interval=255, tps=255 * 30,
                  source_camera=0, playback_fps=60.0, out="f64", device_id=0):
@@ -130,17 +122,6 @@ class HipPlayer:
     def from_header(cls, buf, playback_fps=60.0, out="f64", device_id=0):
         meta, _, _ = parse_header(buf)
         return cls(playback_fps=playback_fps, out=out, device_id=device_id, **meta)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.adder_player_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         self._check(self.L.adder_player_reset(self.h), 0)

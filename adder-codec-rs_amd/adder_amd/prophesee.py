@@ -62,19 +62,10 @@ SYMBOLS = {
     "adder_prophesee_exp_host": (None, [_vp, _vp, _u64]),
     "adder_prophesee_exp_device": (_i32, [_vp, _vp, _u64, _i32]),
 }
-_lib = None
 
 
 def load():
-    global _lib
-    if _lib is None:
-        L = N.load()
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)  # AttributeError if the library does not export it
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
+    return N.bind(SYMBOLS)
 
 
 def exp(x):
@@ -147,10 +138,11 @@ def _device_buffer(t, dev, what):
                          f"contiguous={t.is_contiguous()})")
 
 
-class HipProphesee:
+class HipProphesee(N.Handle):
     """Prophesee::new(ref_time, ..)[.crf(c)] on one device: start() runs the two start-up frames, push() any split
     of the record stream, finish() the end of input.  After a refused push, .bad_index is the stream index of the
     record outside the plane (else None)."""
+    DESTROY = "adder_prophesee_destroy"
 
     def __init__(self, width, height, ref_time=1, crf=NO_CRF, device_id=0):
         self.L = load()
@@ -164,17 +156,6 @@ class HipProphesee:
         self.width, self.height, self.ref_time, self.device_id = width, height, ref_time, device_id
         self.events_per_step = self.L.adder_prophesee_events_per_step(h)
         self.bad_index = None
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.adder_prophesee_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _check(self, rc):
         if rc != N.OK:

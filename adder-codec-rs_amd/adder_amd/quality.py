@@ -11,6 +11,8 @@ import math
 
 import numpy as np
 
+from . import _native as N
+
 
 def calculate_mse(original, reconstructed):
     a = np.asarray(original)
@@ -65,31 +67,22 @@ SYMBOLS = {
     "adder_quality_compute_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     "adder_quality_compute_host": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp]),
 }
-_lib = None
 
 
 def load():
-    global _lib
-    if _lib is None:
-        from . import _native as N
-        L = N.load()
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)  # AttributeError if the library does not export it
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
+    return N.bind(SYMBOLS)
 
 
-class HipQuality:
+class HipQuality(N.Handle):
     """calculate_quality_metrics on the device for batches of u8 frames [n][H][W][C] (C = 1 or 3).
 
     mse / psnr / ssim select the metrics (QualityMetrics' Some / None); every call returns one dict per frame with the
     selected keys.  MSE and PSNR equal calculate_quality_metrics bit for bit; SSIM (percent) is the reference's
     windows bit for bit, summed in a fixed order (NaN when H or W < 8)."""
 
+    DESTROY = "adder_quality_destroy"
+
     def __init__(self, width, height, channels=1, *, mse=True, psnr=True, ssim=False, device_id=0):
-        from . import _native as N
         self.N, self.L = N, load()
         metrics = (MSE if mse else 0) | (PSNR if psnr else 0) | (SSIM if ssim else 0)
         p = AdderQualityParams(abi_version=ABI_VERSION, width=width, height=height, channels=channels,
@@ -101,17 +94,6 @@ class HipQuality:
         self.h, self.params = h, p
         self.width, self.height, self.channels, self.metrics = width, height, channels, metrics
         self.frame_elems = width * height * channels
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.adder_quality_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def map_shape(self, n_frames):
         """The per-window map of n frames: [n][C][H - 7][W - 7] float64 (empty when the plane has no window)."""

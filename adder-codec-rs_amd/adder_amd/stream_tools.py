@@ -58,21 +58,12 @@ SYMBOLS = {
     "adder_stream_info_range": (_i32, [_vp, _pf64, _pf64, _pu64]),
     "adder_stream_format_report": (_sz, [_pp, C.c_uint32, _u64, _u64, _i32, _f64, _f64, _vp, _sz]),
 }
-_lib = None
 META_KEYS = ("width", "height", "channels", "codec_version", "time_mode", "ref_interval", "source_camera", "tps",
              "delta_t_max")
 
 
 def load():
-    global _lib
-    if _lib is None:
-        L = N.load()
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)  # AttributeError if the library does not export it
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
+    return N.bind(SYMBOLS)
 
 
 def _params(meta, out_time_mode=None, device_id=0):
@@ -114,10 +105,11 @@ def format_report(meta, header_bytes, file_bytes, n_events, dynamic_range=False,
     return buf.raw[:n].decode()
 
 
-class _Handle:
+class _Handle(N.Handle):
     """One adder_stream handle.  After a call: .bad_index is the index (within that call's input) of the event that
     stopped it, or None -- the events before it are applied, nothing after it is; .consumed is the number of wire
     records before an EOF record (all of them when there is none)."""
+    DESTROY = "adder_stream_destroy"
 
     def __init__(self, meta, out_time_mode, device_id):
         self.L = load()
@@ -129,17 +121,6 @@ class _Handle:
         self.h, self.params, self.meta = h, p, dict(meta)
         self.record_bytes = 9 if meta["channels"] == 1 else 11
         self.bad_index, self.consumed = None, 0
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.adder_stream_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         self._done(self.L.adder_stream_reset(self.h), C.c_uint64(NO_BAD_EVENT), 0)

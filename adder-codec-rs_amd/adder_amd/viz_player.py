@@ -65,19 +65,10 @@ SYMBOLS = {
     "adder_viz_player_running_frame": (_i32, [_vp, _vp]),
     "adder_viz_schedule_host": (C.c_int64, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _i32, _u32, _i32, _vp, _vp, _u64]),
 }
-_lib = None
 
 
 def load():
-    global _lib
-    if _lib is None:
-        L = N.load()
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)  # AttributeError if the library does not export it
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
+    return N.bind(SYMBOLS)
 
 
 def schedule_host(row, frm, to, last_filled, rows, row_units, buffer_limit, finish=False):
@@ -96,7 +87,7 @@ def schedule_host(row, frm, to, last_filled, rows, row_units, buffer_limit, fini
     return pops[:k], fl[:k]
 
 
-class HipVizPlayer:
+class HipVizPlayer(N.Handle):
     """The player's state on one device.  Every ingest call continues the stream where the last one stopped and
     returns the frames popped during it; finish() ends the stream.
 
@@ -106,6 +97,7 @@ class HipVizPlayer:
 
     A call whose frames do not fit max_frames raises AdderHipError(E_OUT_CAPACITY) with .needed = the count, and
     changes nothing."""
+    DESTROY = "adder_viz_player_destroy"
 
     def __init__(self, width, height, channels=1, *, tps, ref_interval, delta_t_max, output_fps, codec_version=2,
                  time_mode=N.TIME_DELTA_T, source_camera=0, buffer_limit=60, view_mode=0, source_type=0,
@@ -128,17 +120,6 @@ class HipVizPlayer:
         self.shape = (height, width, channels)
         self.units = height * width * channels
         self.bad_index, self.consumed, self.pop_index = None, 0, np.zeros(0, np.int64)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.adder_viz_player_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         self._check(self.L.adder_viz_player_reset(self.h), 0)

@@ -18,60 +18,9 @@
 #include "../../include/adder_dvs.h"
 #include "adder_dvs_kernels.h"
 #include "adder_log1p.hpp"
+#include "adder_wire.hpp"
 
 namespace adder {
-
-struct DvsEv {
-    uint32_t x, y, c, d, t;
-    bool end;  // EOF record or undecodable (raw/stream.rs:177-201: either ends the reading loop)
-};
-
-__device__ __forceinline__ uint32_t be16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
-__device__ __forceinline__ uint32_t be32(const uint8_t *p) {
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-template <int SRC>
-__device__ __forceinline__ DvsEv dvs_load(const void *in, uint64_t i) {
-    DvsEv e;
-    e.end = false;
-    if (SRC == kDvsEvents) {
-        const AdderEvent ev = ((const AdderEvent *)in)[i];
-        e.x = ev.x;
-        e.y = ev.y;
-        e.c = ev.c == 0xffu ? 0u : ev.c;  // `c = None` counts as channel 0
-        e.d = ev.d;
-        e.t = ev.t;
-    } else if (SRC == kDvsWire9) {
-        const uint8_t *p = (const uint8_t *)in + i * 9u;
-        e.x = be16(p);
-        e.y = be16(p + 2);
-        e.c = 0u;
-        e.d = p[4];
-        e.t = be32(p + 5);
-        e.end = e.x == 0xffffu && e.y == 0xffffu;
-    } else {  // 11 bytes: x, y, Option<u8> c (bincode: tag byte, then the value when Some), d, t
-        const uint8_t *p = (const uint8_t *)in + i * 11u;
-        e.x = be16(p);
-        e.y = be16(p + 2);
-        const uint32_t tag = p[4];
-        if (tag == 1u) {
-            e.c = p[5];
-            e.d = p[6];
-            e.t = be32(p + 7);
-        } else {
-            e.c = 0u;
-            e.d = p[5];
-            e.t = be32(p + 6);
-        }
-        e.end = tag > 1u || (e.x == 0xffffu && e.y == 0xffffu);
-    }
-    return e;
-}
-
-__device__ __forceinline__ uint64_t dvs_round_up(uint64_t t, uint64_t ref) {
-    return t % ref == 0u ? t : (t / ref + 1u) * ref;
-}
 
 __global__ void dvs_init_kernel(DvsScalars *sc, uint64_t n) {
     sc->bad = ~0ull;
@@ -85,7 +34,7 @@ __global__ __launch_bounds__(256) void dvs_keys_kernel(const void *__restrict__ 
                                                        DvsScalars *sc) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const DvsEv e = dvs_load<SRC>(in, i);
+    const WireEv e = wire_load<SRC>(in, i);
     uint32_t key = a.units;  // sorted behind every unit, never walked
     if (e.end) {
         atomicMin(&sc->eof, (unsigned long long)i);
@@ -108,7 +57,7 @@ __global__ __launch_bounds__(256) void dvs_ln_kernel(const void *__restrict__ in
     const uint32_t u = keys[j];
     if (u >= a.units) return;
     const uint32_t i = idx[j];
-    const DvsEv e = dvs_load<SRC>(in, i);
+    const WireEv e = wire_load<SRC>(in, i);
     const bool head = j == 0u || keys[j - 1] != u;
     const bool init0 = a.cur_init[u] != 0u;
     const bool first = head && !init0;  // the unit's first event ever (main.rs:251-265)
@@ -120,9 +69,9 @@ __global__ __launch_bounds__(256) void dvs_ln_kernel(const void *__restrict__ in
         if (head) {
             old_t = a.cur_t[u];
         } else {
-            const uint32_t pt = dvs_load<SRC>(in, idx[j - 1]).t;
+            const uint32_t pt = wire_load<SRC>(in, idx[j - 1]).t;
             const bool prev_first = !init0 && (j - 1u == 0u || keys[j - 2] != u);
-            old_t = (a.framed && !prev_first) ? dvs_round_up(pt, a.ref) : (uint64_t)pt;
+            old_t = (a.framed && !prev_first) ? wire_round_up(pt, a.ref) : (uint64_t)pt;
         }
         const uint32_t o = (uint32_t)old_t;
         t = t > o ? t - o : 0u;
@@ -139,7 +88,7 @@ __global__ __launch_bounds__(256) void dvs_walk_kernel(uint64_t n, DvsArgs a, co
     if (j0 >= n) return;
     const uint32_t u = keys[j0];
     if (u >= a.units || (j0 > 0u && keys[j0 - 1] == u)) return;  // a thread per run of one unit
-    const uint64_t lim = sc->bad < sc->eof ? sc->bad : sc->eof;
+    const uint64_t lim = wire_limit(sc->bad, sc->eof);
     bool init = a.cur_init[u] != 0u;
     double ln = a.cur_ln[u];
     uint64_t pt = a.cur_t[u];
@@ -156,7 +105,7 @@ __global__ __launch_bounds__(256) void dvs_walk_kernel(uint64_t n, DvsArgs a, co
         }
         const uint64_t old_t = pt;
         pt = a.delta_t ? pt + t : (uint64_t)t;
-        if (a.framed) pt = dvs_round_up(pt, a.ref);
+        if (a.framed) pt = wire_round_up(pt, a.ref);
         if (d == 255u) continue;  // D_EMPTY: the time moved, nothing fires
         const double nw = s_ln[j];
         const bool win = nw > 0.406 && nw < 0.407;
@@ -196,7 +145,7 @@ __global__ __launch_bounds__(256) void dvs_scatter_kernel(const void *__restrict
     const uint64_t o = offs[i];
     if (i == n - 1u) sc->total = o + (f != 0u ? 1u : 0u);
     if (f == 0u || o >= out_cap) return;
-    const DvsEv e = dvs_load<SRC>(in, i);
+    const WireEv e = wire_load<SRC>(in, i);
     const uint32_t p = f - 1u;
     if (out_format == ADDER_DVS_OUT_DAT) {
         uint2 r;
@@ -287,9 +236,9 @@ static hipError_t dvs_convert_src(const DvsArgs &a, const void *in, uint64_t n, 
 hipError_t dvs_convert(const DvsArgs &a, int source, const void *in, uint64_t n, int out_format, void *out,
                        uint64_t out_cap, const DvsScratch &s, hipStream_t stream) {
     if (n == 0u) return hipSuccess;
-    if (source == kDvsEvents) return dvs_convert_src<kDvsEvents>(a, in, n, out_format, out, out_cap, s, stream);
-    if (source == kDvsWire9) return dvs_convert_src<kDvsWire9>(a, in, n, out_format, out, out_cap, s, stream);
-    return dvs_convert_src<kDvsWire11>(a, in, n, out_format, out, out_cap, s, stream);
+    if (source == kSrcEvents) return dvs_convert_src<kSrcEvents>(a, in, n, out_format, out, out_cap, s, stream);
+    if (source == kSrcWire9) return dvs_convert_src<kSrcWire9>(a, in, n, out_format, out, out_cap, s, stream);
+    return dvs_convert_src<kSrcWire11>(a, in, n, out_format, out, out_cap, s, stream);
 }
 
 size_t dvs_sort_temp_bytes(uint64_t n) {

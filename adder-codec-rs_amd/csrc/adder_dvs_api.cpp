@@ -4,15 +4,13 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <new>
-#include <string>
 
 #include "../../include/adder_dvs.h"
+#include "adder_api_util.hpp"
 #include "adder_dvs_kernels.h"
 #include "adder_log1p.hpp"
+#include "adder_wire.hpp"
 
 using namespace adder;
 
@@ -40,30 +38,18 @@ struct AdderDvs {
 };
 
 static int dfail(AdderDvs *v, int code, const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    api_fail(v ? v->err : g_dvs_create_error, code, fmt, ap);
     va_end(ap);
-    if (v)
-        v->err = buf;
-    else
-        g_dvs_create_error = buf;
     return code;
 }
 
-#define DHIPCHK(v, expr)                                                                                        \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess)                                                                                   \
-            return dfail(v, ADDER_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#define DHIPCHK(v, expr) ADDER_HIPCHK(dfail, v, expr, #expr)
 
 static void free_scratch(AdderDvs *v) {
-    void *bufs[] = {v->s.keys0, v->s.keys1, v->s.idx0, v->s.idx1, v->s.s_ln, v->s.s_td,
-                    v->s.flag,  v->s.tout,  v->s.offs, v->s.temp};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    api_free_all({v->s.keys0, v->s.keys1, v->s.idx0, v->s.idx1, v->s.s_ln, v->s.s_td, v->s.flag, v->s.tout, v->s.offs,
+                  v->s.temp});
     DvsScalars *sc = v->s.sc;
     v->s = DvsScratch{};
     v->s.sc = sc;
@@ -71,9 +57,7 @@ static void free_scratch(AdderDvs *v) {
 }
 
 static void free_sort(AdderDvs *v) {
-    if (v->sk) (void)hipFree(v->sk);
-    if (v->sort_tmp) (void)hipFree(v->sort_tmp);
-    if (v->sort_temp) (void)hipFree(v->sort_temp);
+    api_free_all({v->sk, v->sort_tmp, v->sort_temp});
     v->sk = nullptr;
     v->sort_tmp = v->sort_temp = nullptr;
     v->sort_cap = 0;
@@ -87,10 +71,8 @@ static void dvs_free(AdderDvs *v) {
     (void)hipDeviceSynchronize();
     free_scratch(v);
     free_sort(v);
-    void *bufs[] = {v->a.cur_init, v->a.nxt_init, v->a.cur_ln, v->a.nxt_ln, v->a.cur_t, v->a.nxt_t,
-                    v->s.sc,       v->d_in,       v->d_out};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    api_free_all({v->a.cur_init, v->a.nxt_init, v->a.cur_ln, v->a.nxt_ln, v->a.cur_t, v->a.nxt_t, v->s.sc, v->d_in,
+                  v->d_out});
     if (v->h_sc) (void)hipHostFree(v->h_sc);
     if (v->stream) (void)hipStreamDestroy(v->stream);
     delete v;
@@ -115,45 +97,25 @@ static int ensure_scratch(AdderDvs *v, uint64_t n) {
     return ADDER_OK;
 }
 
-static int grow(AdderDvs *v, void **buf, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return ADDER_OK;
-    if (*buf) DHIPCHK(v, hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    DHIPCHK(v, hipMalloc(buf, bytes));
-    *cap = bytes;
-    return ADDER_OK;
-}
-
 static size_t record_bytes(int fmt) { return fmt == ADDER_DVS_OUT_DAT ? 8u : sizeof(AdderDvsEvent); }
 
 extern "C" int adder_dvs_parse_header(const uint8_t *b, size_t len, AdderDvsParams *p, uint32_t *header_bytes,
                                       uint32_t *event_bytes) {
-    // header.rs:14-25 + encoder.rs:170-229: "adder", version, endianness 'b', u16 w, h, u32 tps, ref, delta_t_max,
-    // u8 event size, channels; then u32 source camera (v >= 1), time mode (v >= 2), adu interval (v >= 3), big-endian
-    if (!b || !p || len < 25 || memcmp(b, "adder", 5) != 0 || b[6] != 'b' || b[5] > 3) return ADDER_E_BAD_PARAMS;
-    const uint32_t version = b[5];
-    const uint32_t hdr = 25u + 4u * version;
-    if (len < hdr) return ADDER_E_BAD_PARAMS;
-    auto be16 = [&](size_t o) { return (uint32_t)((b[o] << 8) | b[o + 1]); };
-    auto be32 = [&](size_t o) {
-        return ((uint32_t)b[o] << 24) | ((uint32_t)b[o + 1] << 16) | ((uint32_t)b[o + 2] << 8) | b[o + 3];
-    };
+    RawHeader h;
+    if (!p || !raw_header_parse(b, len, &h) || !raw_header_events_ok(h)) return ADDER_E_BAD_PARAMS;
     AdderDvsParams q{};
     q.abi_version = ADDER_DVS_ABI_VERSION;
-    q.width = (uint16_t)be16(7);
-    q.height = (uint16_t)be16(9);
-    q.ref_interval = be32(15);
-    const uint32_t esize = b[23];
-    q.channels = b[24];
-    q.source_camera = version >= 1 ? be32(25) : 0u;
-    q.time_mode = (uint8_t)(version >= 2 ? be32(29) : 0u);
+    q.width = (uint16_t)h.width;
+    q.height = (uint16_t)h.height;
+    q.ref_interval = h.ref_interval;
+    q.channels = (uint8_t)h.channels;
+    q.source_camera = h.source_camera;
+    q.time_mode = (uint8_t)h.time_mode;  // the low byte, whatever it says: adder_dvs_create reads 0 as DeltaT
     q.theta = 0.01;
     q.device_id = 0;
-    if (q.channels == 0 || esize != (q.channels == 1 ? 9u : 11u)) return ADDER_E_BAD_PARAMS;
     *p = q;
-    if (header_bytes) *header_bytes = hdr;
-    if (event_bytes) *event_bytes = esize;
+    if (header_bytes) *header_bytes = h.header_bytes;
+    if (event_bytes) *event_bytes = h.event_size;
     return ADDER_OK;
 }
 
@@ -166,15 +128,7 @@ extern "C" int adder_dvs_create(const AdderDvsParams *p, AdderDvs **out) {
     if (p->width == 0 || p->height == 0 || (p->channels != 1 && p->channels != 3))
         return dfail(nullptr, ADDER_E_BAD_PARAMS, "plane %ux%ux%u", p->width, p->height, p->channels);
     if (p->ref_interval == 0) return dfail(nullptr, ADDER_E_BAD_PARAMS, "ref_interval must be > 0");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return dfail(nullptr, ADDER_E_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (p->device_id < 0 || p->device_id >= ndev)
-        return dfail(nullptr, ADDER_E_BAD_PARAMS, "device_id %d of %d", p->device_id, ndev);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device_id) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return dfail(nullptr, ADDER_E_NO_DEVICE, "device %d is not gfx950; this library is built for gfx950 only",
-                     p->device_id);
+    if (const int rc = api_check_device(p->device_id, g_dvs_create_error)) return rc;
     AdderDvs *v = new (std::nothrow) AdderDvs();
     if (!v) return dfail(nullptr, ADDER_E_BAD_PARAMS, "out of host memory");
     v->p = *p;
@@ -268,21 +222,19 @@ static int convert(AdderDvs *v, int source, const void *d_in, uint64_t n, int fm
 
 extern "C" int adder_dvs_convert_device(AdderDvs *v, const AdderEvent *d_events, uint64_t n, int fmt, void *d_out,
                                         uint64_t out_cap, uint64_t *n_out, uint64_t *bad_index, void *stream) {
-    return convert(v, kDvsEvents, d_events, n, fmt, d_out, out_cap, n_out, bad_index, nullptr, (hipStream_t)stream);
+    return convert(v, kSrcEvents, d_events, n, fmt, d_out, out_cap, n_out, bad_index, nullptr, (hipStream_t)stream);
 }
-
-static int wire_source(AdderDvs *v) { return v->p.channels == 1 ? kDvsWire9 : kDvsWire11; }
 
 extern "C" int adder_dvs_convert_wire_device(AdderDvs *v, const uint8_t *d_wire, uint64_t n_records, int fmt,
                                              void *d_out, uint64_t out_cap, uint64_t *n_out, uint64_t *bad_index,
                                              uint64_t *n_consumed, void *stream) {
     if (!v) return ADDER_E_BAD_PARAMS;
-    return convert(v, wire_source(v), d_wire, n_records, fmt, d_out, out_cap, n_out, bad_index, n_consumed,
+    return convert(v, wire_source(v->p.channels), d_wire, n_records, fmt, d_out, out_cap, n_out, bad_index, n_consumed,
                    (hipStream_t)stream);
 }
 
-static int convert_host(AdderDvs *v, int source, const void *in, uint64_t n, size_t in_rec, int fmt, void *out,
-                        uint64_t out_cap, uint64_t *n_out, uint64_t *bad_index, uint64_t *n_consumed) {
+static int convert_host(AdderDvs *v, int source, const void *in, uint64_t n, int fmt, void *out, uint64_t out_cap,
+                        uint64_t *n_out, uint64_t *bad_index, uint64_t *n_consumed) {
     if (!v) return ADDER_E_BAD_PARAMS;
     if (n > (uint64_t)INT32_MAX) return dfail(v, ADDER_E_BAD_PARAMS, "too many events in one call");
     if (n > 0 && !in) return dfail(v, ADDER_E_BAD_PARAMS, "null input");
@@ -290,12 +242,10 @@ static int convert_host(AdderDvs *v, int source, const void *in, uint64_t n, siz
     DHIPCHK(v, hipSetDevice(v->p.device_id));
     const size_t rb = record_bytes(fmt);
     const uint64_t dcap = out_cap < n ? out_cap : n;  // an input event fires at most once
-    int rc = grow(v, &v->d_in, &v->d_in_cap, n * in_rec + 1u);
-    if (rc == ADDER_OK) rc = grow(v, &v->d_out, &v->d_out_cap, dcap * rb + 1u);
-    if (rc != ADDER_OK) return rc;
-    if (n) DHIPCHK(v, hipMemcpyAsync(v->d_in, in, n * in_rec, hipMemcpyHostToDevice, v->stream));
+    DHIPCHK(v, api_grow(&v->d_out, &v->d_out_cap, dcap * rb + 1u));
+    DHIPCHK(v, api_stage_input(&v->d_in, &v->d_in_cap, in, n * wire_record_bytes(source), v->stream));
     uint64_t got = 0;
-    rc = convert(v, source, v->d_in, n, fmt, v->d_out, dcap, &got, bad_index, n_consumed, v->stream);
+    const int rc = convert(v, source, v->d_in, n, fmt, v->d_out, dcap, &got, bad_index, n_consumed, v->stream);
     if (n_out) *n_out = got;
     if ((rc == ADDER_OK || rc == ADDER_DVS_E_BAD_EVENT) && got)
         DHIPCHK(v, hipMemcpy(out, v->d_out, got * rb, hipMemcpyDeviceToHost));
@@ -304,15 +254,15 @@ static int convert_host(AdderDvs *v, int source, const void *in, uint64_t n, siz
 
 extern "C" int adder_dvs_convert_host(AdderDvs *v, const AdderEvent *events, uint64_t n, int fmt, void *out,
                                       uint64_t out_cap, uint64_t *n_out, uint64_t *bad_index) {
-    return convert_host(v, kDvsEvents, events, n, sizeof(AdderEvent), fmt, out, out_cap, n_out, bad_index, nullptr);
+    return convert_host(v, kSrcEvents, events, n, fmt, out, out_cap, n_out, bad_index, nullptr);
 }
 
 extern "C" int adder_dvs_convert_wire_host(AdderDvs *v, const uint8_t *wire, uint64_t n_records, int fmt, void *out,
                                            uint64_t out_cap, uint64_t *n_out, uint64_t *bad_index,
                                            uint64_t *n_consumed) {
     if (!v) return ADDER_E_BAD_PARAMS;
-    return convert_host(v, wire_source(v), wire, n_records, v->p.channels == 1 ? 9u : 11u, fmt, out, out_cap, n_out,
-                        bad_index, n_consumed);
+    return convert_host(v, wire_source(v->p.channels), wire, n_records, fmt, out, out_cap, n_out, bad_index,
+                        n_consumed);
 }
 
 extern "C" int adder_dvs_sort_device(AdderDvs *v, void *d_records, uint64_t n, int fmt, void *stream) {

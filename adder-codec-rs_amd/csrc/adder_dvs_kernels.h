@@ -5,7 +5,6 @@
 
 namespace adder {
 
-enum DvsSource : int { kDvsEvents = 0, kDvsWire9 = 1, kDvsWire11 = 2 };
 
 struct DvsScalars {  // device words of one call, read back once at its end
     unsigned long long bad;  // smallest index of a bad event (UINT64_MAX: none)

@@ -4,16 +4,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <deque>
 #include <new>
 #include <cstdlib>
-#include <string>
 #include <vector>
 
 #include "../../include/adder_framer.h"
+#include "adder_api_util.hpp"
 #include "adder_framer_features.h"
 #include "adder_framer_kernels.h"
 
@@ -78,35 +75,21 @@ struct AdderFramer {
 };
 
 static int ffail(AdderFramer *fr, int code, const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    api_fail(fr ? fr->err : g_framer_create_error, code, fmt, ap);
     va_end(ap);
-    if (fr)
-        fr->err = buf;
-    else
-        g_framer_create_error = buf;
     return code;
 }
 
-#define FHIPCHK(fr, expr)                                                                        \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return ffail(fr, ADDER_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                         __FILE__, __LINE__);                                                    \
-    } while (0)
+#define FHIPCHK(fr, expr) ADDER_HIPCHK(ffail, fr, expr, #expr)
 
 static void framer_free(AdderFramer *fr) {
     if (!fr) return;
     (void)hipSetDevice(fr->device);
     if (fr->stream) (void)hipStreamSynchronize(fr->stream);
-    for (void *p : {(void *)fr->px, (void *)fr->ring, (void *)fr->status,
-                    (void *)fr->minmax, (void *)fr->d_events, (void *)fr->d_out, (void *)fr->d_offs, (void *)fr->d_tile_off,
-                    (void *)fr->plane, (void *)fr->carry, (void *)fr->feat_count, (void *)fr->feat_runs,
-                    (void *)fr->feat_scratch, (void *)fr->feat_out})
-        if (p) (void)hipFree(p);
+    api_free_all({fr->px, fr->ring, fr->status, fr->minmax, fr->d_events, fr->d_out, fr->d_offs, fr->d_tile_off, fr->plane,
+                  fr->carry, fr->feat_count, fr->feat_runs, fr->feat_scratch, fr->feat_out});
     if (fr->h_offs) (void)hipHostFree(fr->h_offs);
     if (fr->h_offs_big) (void)hipHostFree(fr->h_offs_big);
     for (hipEvent_t e : fr->h_offs_done)

@@ -21,58 +21,9 @@
 #include "../../include/adder_player.h"
 #include "adder_player_kernels.h"
 #include "adder_player_logic.hpp"
+#include "adder_wire.hpp"
 
 namespace adder {
-
-struct PlayerEv {
-    uint32_t x, y, c, d, t;
-    bool end;  // EOF record or undecodable (raw/stream.rs:177-201: either ends the reading loop)
-};
-
-__device__ __forceinline__ uint32_t pl_be16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
-__device__ __forceinline__ uint32_t pl_be32(const uint8_t *p) {
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-template <int SRC>
-__device__ __forceinline__ PlayerEv player_load(const void *in, uint64_t i) {
-    PlayerEv e;
-    e.end = false;
-    if (SRC == kPlayerEvents) {
-        const AdderEvent ev = ((const AdderEvent *)in)[i];
-        e.x = ev.x;
-        e.y = ev.y;
-        e.c = ev.c == 0xffu ? 0u : ev.c;  // `c = None` counts as channel 0
-        e.d = ev.d;
-        e.t = ev.t;
-    } else if (SRC == kPlayerWire9) {
-        const uint8_t *p = (const uint8_t *)in + i * 9u;
-        e.x = pl_be16(p);
-        e.y = pl_be16(p + 2);
-        e.c = 0u;
-        e.d = p[4];
-        e.t = pl_be32(p + 5);
-        e.end = e.x == 0xffffu && e.y == 0xffffu;
-    } else {  // 11 bytes: x, y, Option<u8> c (bincode: tag byte, then the value when Some), d, t
-        const uint8_t *p = (const uint8_t *)in + i * 11u;
-        e.x = pl_be16(p);
-        e.y = pl_be16(p + 2);
-        const uint32_t tag = p[4];
-        if (tag == 1u) {
-            e.c = p[5];
-            e.d = p[6];
-            e.t = pl_be32(p + 7);
-        } else {
-            e.c = 0u;
-            e.d = p[5];
-            e.t = pl_be32(p + 6);
-        }
-        e.end = tag > 1u || (e.x == 0xffffu && e.y == 0xffffu);
-    }
-    return e;
-}
-
-__device__ __forceinline__ uint64_t player_lim(const PlayerScalars *sc) { return sc->bad < sc->eof ? sc->bad : sc->eof; }
 
 __global__ void player_init_kernel(PlayerScalars *sc, uint64_t n, uint32_t *cand, uint32_t cur0) {
     sc->bad = ~0ull;
@@ -88,7 +39,7 @@ __global__ __launch_bounds__(256) void player_keys_kernel(const void *__restrict
                                                           PlayerScalars *sc) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const PlayerEv e = player_load<SRC>(in, i);
+    const WireEv e = wire_load<SRC>(in, i);
     uint32_t key = a.units;
     if (e.end) {
         atomicMin(&sc->eof, (unsigned long long)i);
@@ -114,17 +65,17 @@ __global__ __launch_bounds__(256) void player_value_kernel(const void *__restric
     const uint32_t u = keys[j];
     if (u >= a.units) return;
     const uint32_t i = idx[j];
-    const PlayerEv e = player_load<SRC>(in, i);
+    const WireEv e = wire_load<SRC>(in, i);
     if (!a.absolute) {
         s_val[j] = player_value(e.d, e.t, a.ref_f, a.m);
         s_ts[j] = e.t;  // the walk turns it into last_ts
         return;
     }
     const bool head = j == 0u || keys[j - 1] != u;
-    const uint32_t prev = head ? a.last_ts[u] : player_round_up(player_load<SRC>(in, idx[j - 1]).t, a.ref);
+    const uint32_t prev = head ? a.last_ts[u] : player_round_up(wire_load<SRC>(in, idx[j - 1]).t, a.ref);
     s_val[j] = player_value(e.d, e.t - prev, a.ref_f, a.m);
     s_ts[j] = player_round_up(e.t, a.ref);
-    if (i < player_lim(sc)) cand[(uint64_t)i + 1u] = e.t;
+    if (i < wire_limit(sc->bad, sc->eof)) cand[(uint64_t)i + 1u] = e.t;
 }
 
 // A thread per run: last_ts += t, rounded up, in u32 (the reference's wrap-around exactly).
@@ -135,7 +86,7 @@ __global__ __launch_bounds__(256) void player_walk_kernel(uint64_t n, PlayerArgs
     if (j0 >= n) return;
     const uint32_t u = keys[j0];
     if (u >= a.units || (j0 > 0u && keys[j0 - 1] == u)) return;
-    const uint64_t lim = player_lim(sc);
+    const uint64_t lim = wire_limit(sc->bad, sc->eof);
     uint32_t ts = a.last_ts[u];
     for (uint64_t j = j0; j < n && keys[j] == u; ++j) {
         const uint32_t i = idx[j];
@@ -158,7 +109,7 @@ __global__ __launch_bounds__(256) void player_mark_kernel(uint64_t n, int final_
                                                           PlayerScalars *sc) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i > n) return;
-    const uint64_t lim = player_lim(sc);
+    const uint64_t lim = wire_limit(sc->bad, sc->eof);
     // checks: one before every applied event; one more where the stream ends (EOF record) or the caller says so
     const bool last = sc->bad < sc->eof ? false : (sc->eof < n || final_check != 0);
     const uint64_t nchk = lim + (last ? 1u : 0u);
@@ -330,9 +281,9 @@ static hipError_t player_schedule_src(const PlayerArgs &a, const void *in, uint6
 
 hipError_t player_schedule(const PlayerArgs &a, int source, const void *in, uint64_t n, int final_check, uint32_t cur0,
                            uint64_t f0, PlayerScratch &s, hipStream_t stream) {
-    if (source == kPlayerEvents) return player_schedule_src<kPlayerEvents>(a, in, n, final_check, cur0, f0, s, stream);
-    if (source == kPlayerWire9) return player_schedule_src<kPlayerWire9>(a, in, n, final_check, cur0, f0, s, stream);
-    return player_schedule_src<kPlayerWire11>(a, in, n, final_check, cur0, f0, s, stream);
+    if (source == kSrcEvents) return player_schedule_src<kSrcEvents>(a, in, n, final_check, cur0, f0, s, stream);
+    if (source == kSrcWire9) return player_schedule_src<kSrcWire9>(a, in, n, final_check, cur0, f0, s, stream);
+    return player_schedule_src<kSrcWire11>(a, in, n, final_check, cur0, f0, s, stream);
 }
 
 hipError_t player_handout(const PlayerArgs &a, uint64_t n, uint64_t lim, uint64_t n_frames, void *d_frames,

@@ -5,15 +5,13 @@
 
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <new>
-#include <string>
 
 #include "../../include/adder_player.h"
+#include "adder_api_util.hpp"
 #include "adder_player_kernels.h"
 #include "adder_player_logic.hpp"
+#include "adder_wire.hpp"
 
 using namespace adder;
 
@@ -36,33 +34,21 @@ struct AdderPlayer {
 };
 
 static int pfail(AdderPlayer *v, int code, const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    api_fail(v ? v->err : g_player_create_error, code, fmt, ap);
     va_end(ap);
-    if (v)
-        v->err = buf;
-    else
-        g_player_create_error = buf;
     return code;
 }
 
-#define PHIPCHK(v, expr)                                                                                        \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess)                                                                                   \
-            return pfail(v, ADDER_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#define PHIPCHK(v, expr) ADDER_HIPCHK(pfail, v, expr, #expr)
 
 static size_t elem_bytes(const AdderPlayer *v) { return v->p.out_type == ADDER_PLAYER_U8 ? 1u : 8u; }
 static size_t frame_bytes(const AdderPlayer *v) { return (size_t)v->a.units * elem_bytes(v); }
 
 static void free_scratch(AdderPlayer *v) {
-    void *bufs[] = {v->s.keys0, v->s.keys1, v->s.idx0, v->s.idx1, v->s.s_val, v->s.s_ts, v->s.cand,
-                    v->s.cur,   v->s.term,  v->s.pmin, v->s.mark, v->s.offs,  v->s.pos,  v->s.temp};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    api_free_all({v->s.keys0, v->s.keys1, v->s.idx0, v->s.idx1, v->s.s_val, v->s.s_ts, v->s.cand, v->s.cur, v->s.term,
+                  v->s.pmin, v->s.mark, v->s.offs, v->s.pos, v->s.temp});
     PlayerScalars *sc = v->s.sc;
     v->s = PlayerScratch{};
     v->s.sc = sc;
@@ -75,9 +61,7 @@ static void player_free(AdderPlayer *v) {
     if (v->stream) (void)hipStreamSynchronize(v->stream);
     (void)hipDeviceSynchronize();
     free_scratch(v);
-    void *bufs[] = {v->a.last_ts, v->a.display, v->a.run_lo, v->s.sc, v->d_in, v->d_out};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    api_free_all({v->a.last_ts, v->a.display, v->a.run_lo, v->s.sc, v->d_in, v->d_out});
     if (v->h_sc) (void)hipHostFree(v->h_sc);
     if (v->stream) (void)hipStreamDestroy(v->stream);
     delete v;
@@ -108,45 +92,25 @@ static int ensure_scratch(AdderPlayer *v, uint64_t n) {
     return ADDER_OK;
 }
 
-static int grow(AdderPlayer *v, void **buf, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return ADDER_OK;
-    if (*buf) PHIPCHK(v, hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    PHIPCHK(v, hipMalloc(buf, bytes));
-    *cap = bytes;
-    return ADDER_OK;
-}
-
 extern "C" int adder_player_parse_header(const uint8_t *b, size_t len, AdderPlayerParams *p, uint32_t *header_bytes,
                                          uint32_t *event_bytes) {
-    // header.rs:14-25 + encoder.rs:170-229: "adder", version, endianness 'b', u16 w, h, u32 tps, ref, delta_t_max,
-    // u8 event size, channels; then u32 source camera (v >= 1), time mode (v >= 2), adu interval (v >= 3), big-endian
-    if (!b || !p || len < 25 || memcmp(b, "adder", 5) != 0 || b[6] != 'b' || b[5] > 3) return ADDER_E_BAD_PARAMS;
-    const uint32_t version = b[5];
-    const uint32_t hdr = 25u + 4u * version;
-    if (len < hdr) return ADDER_E_BAD_PARAMS;
-    auto be16 = [&](size_t o) { return (uint32_t)((b[o] << 8) | b[o + 1]); };
-    auto be32 = [&](size_t o) {
-        return ((uint32_t)b[o] << 24) | ((uint32_t)b[o + 1] << 16) | ((uint32_t)b[o + 2] << 8) | b[o + 3];
-    };
+    RawHeader h;
+    if (!p || !raw_header_parse(b, len, &h) || !raw_header_events_ok(h)) return ADDER_E_BAD_PARAMS;
     AdderPlayerParams q{};
     q.abi_version = ADDER_PLAYER_ABI_VERSION;
-    q.width = (uint16_t)be16(7);
-    q.height = (uint16_t)be16(9);
-    q.tps = be32(11);
-    q.ref_interval = be32(15);
-    const uint32_t esize = b[23];
-    q.channels = b[24];
-    q.source_camera = version >= 1 ? be32(25) : 0u;
-    q.time_mode = (uint8_t)(version >= 2 ? be32(29) : 0u);
+    q.width = (uint16_t)h.width;
+    q.height = (uint16_t)h.height;
+    q.tps = h.tps;
+    q.ref_interval = h.ref_interval;
+    q.channels = (uint8_t)h.channels;
+    q.source_camera = h.source_camera;
+    q.time_mode = (uint8_t)h.time_mode;  // the low byte, whatever it says: adder_player_create reads 1 as AbsoluteT
     q.playback_fps = 60.0;
     q.out_type = ADDER_PLAYER_F64;
     q.device_id = 0;
-    if (q.channels == 0 || esize != (q.channels == 1 ? 9u : 11u)) return ADDER_E_BAD_PARAMS;
     *p = q;
-    if (header_bytes) *header_bytes = hdr;
-    if (event_bytes) *event_bytes = esize;
+    if (header_bytes) *header_bytes = h.header_bytes;
+    if (event_bytes) *event_bytes = h.event_size;
     return ADDER_OK;
 }
 
@@ -166,15 +130,7 @@ extern "C" int adder_player_create(const AdderPlayerParams *p, AdderPlayer **out
                      p->source_camera);
     if (p->out_type != ADDER_PLAYER_F64 && p->out_type != ADDER_PLAYER_U8)
         return pfail(nullptr, ADDER_E_BAD_PARAMS, "out_type %d", p->out_type);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return pfail(nullptr, ADDER_E_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (p->device_id < 0 || p->device_id >= ndev)
-        return pfail(nullptr, ADDER_E_BAD_PARAMS, "device_id %d of %d", p->device_id, ndev);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device_id) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return pfail(nullptr, ADDER_E_NO_DEVICE, "device %d is not gfx950; this library is built for gfx950 only",
-                     p->device_id);
+    if (const int rc = api_check_device(p->device_id, g_player_create_error)) return rc;
     AdderPlayer *v = new (std::nothrow) AdderPlayer();
     if (!v) return pfail(nullptr, ADDER_E_BAD_PARAMS, "out of host memory");
     v->p = *p;
@@ -267,8 +223,7 @@ static int play(AdderPlayer *v, int source, const void *d_in, uint64_t n, int fi
         return pfail(v, ADDER_E_BAD_PARAMS, "%llu frames in one call: play fewer records at a time",
                      (unsigned long long)sc.total);
     if (h_frames) {
-        rc = grow(v, &v->d_out, &v->d_out_cap, sc.total * fb + 8u);
-        if (rc != ADDER_OK) return rc;
+        PHIPCHK(v, api_grow(&v->d_out, &v->d_out_cap, sc.total * fb + 8u));
         d_frames = v->d_out;
     }
     PHIPCHK(v, player_handout(v->a, n, lim, sc.total, d_frames, v->s, stream));
@@ -286,11 +241,9 @@ static int play(AdderPlayer *v, int source, const void *d_in, uint64_t n, int fi
     return ADDER_OK;
 }
 
-static int wire_source(const AdderPlayer *v) { return v->p.channels == 1 ? kPlayerWire9 : kPlayerWire11; }
-
 extern "C" int adder_player_play_device(AdderPlayer *v, const AdderEvent *d_events, uint64_t n, void *d_frames,
                                         uint64_t frame_cap, uint64_t *n_frames, uint64_t *bad_index, void *stream) {
-    return play(v, kPlayerEvents, d_events, n, 0, d_frames, nullptr, frame_cap, n_frames, bad_index, nullptr,
+    return play(v, kSrcEvents, d_events, n, 0, d_frames, nullptr, frame_cap, n_frames, bad_index, nullptr,
                 (hipStream_t)stream);
 }
 
@@ -298,26 +251,24 @@ extern "C" int adder_player_play_wire_device(AdderPlayer *v, const uint8_t *d_wi
                                              uint64_t frame_cap, uint64_t *n_frames, uint64_t *bad_index,
                                              uint64_t *n_consumed, void *stream) {
     if (!v) return ADDER_E_BAD_PARAMS;
-    return play(v, wire_source(v), d_wire, n_records, 0, d_frames, nullptr, frame_cap, n_frames, bad_index, n_consumed,
-                (hipStream_t)stream);
+    return play(v, wire_source(v->p.channels), d_wire, n_records, 0, d_frames, nullptr, frame_cap, n_frames, bad_index,
+                n_consumed, (hipStream_t)stream);
 }
 
 extern "C" int adder_player_finish(AdderPlayer *v, void *d_frames, uint64_t frame_cap, uint64_t *n_frames,
                                    void *stream) {
-    return play(v, kPlayerEvents, nullptr, 0, 1, d_frames, nullptr, frame_cap, n_frames, nullptr, nullptr,
+    return play(v, kSrcEvents, nullptr, 0, 1, d_frames, nullptr, frame_cap, n_frames, nullptr, nullptr,
                 (hipStream_t)stream);
 }
 
-static int play_host(AdderPlayer *v, int source, const void *in, uint64_t n, size_t in_rec, void *frames,
-                     uint64_t frame_cap, uint64_t *n_frames, uint64_t *bad_index, uint64_t *n_consumed) {
+static int play_host(AdderPlayer *v, int source, const void *in, uint64_t n, void *frames, uint64_t frame_cap,
+                     uint64_t *n_frames, uint64_t *bad_index, uint64_t *n_consumed) {
     if (!v) return ADDER_E_BAD_PARAMS;
     if (n > (uint64_t)INT32_MAX - 1u) return pfail(v, ADDER_E_BAD_PARAMS, "too many records in one call");
     if (n > 0 && !in) return pfail(v, ADDER_E_BAD_PARAMS, "null input");
     if (frame_cap > 0 && !frames) return pfail(v, ADDER_E_BAD_PARAMS, "null frames");
     PHIPCHK(v, hipSetDevice(v->p.device_id));
-    int rc = grow(v, &v->d_in, &v->d_in_cap, n * in_rec + 1u);
-    if (rc != ADDER_OK) return rc;
-    if (n) PHIPCHK(v, hipMemcpyAsync(v->d_in, in, n * in_rec, hipMemcpyHostToDevice, v->stream));
+    PHIPCHK(v, api_stage_input(&v->d_in, &v->d_in_cap, in, n * wire_record_bytes(source), v->stream));
     static uint8_t none;  // a non-null host target for a capacity of zero
     return play(v, source, v->d_in, n, 0, nullptr, frames ? frames : &none, frame_cap, n_frames, bad_index, n_consumed,
                 v->stream);
@@ -325,15 +276,14 @@ static int play_host(AdderPlayer *v, int source, const void *in, uint64_t n, siz
 
 extern "C" int adder_player_play_host(AdderPlayer *v, const AdderEvent *events, uint64_t n, void *frames,
                                       uint64_t frame_cap, uint64_t *n_frames, uint64_t *bad_index) {
-    return play_host(v, kPlayerEvents, events, n, sizeof(AdderEvent), frames, frame_cap, n_frames, bad_index, nullptr);
+    return play_host(v, kSrcEvents, events, n, frames, frame_cap, n_frames, bad_index, nullptr);
 }
 
 extern "C" int adder_player_play_wire_host(AdderPlayer *v, const uint8_t *wire, uint64_t n_records, void *frames,
                                            uint64_t frame_cap, uint64_t *n_frames, uint64_t *bad_index,
                                            uint64_t *n_consumed) {
     if (!v) return ADDER_E_BAD_PARAMS;
-    return play_host(v, wire_source(v), wire, n_records, v->p.channels == 1 ? 9u : 11u, frames, frame_cap, n_frames,
-                     bad_index, n_consumed);
+    return play_host(v, wire_source(v->p.channels), wire, n_records, frames, frame_cap, n_frames, bad_index, n_consumed);
 }
 
 extern "C" int adder_player_display_device(AdderPlayer *v, void *d_frame, void *stream) {
@@ -350,8 +300,7 @@ extern "C" int adder_player_display(AdderPlayer *v, void *frame) {
     if (!frame) return pfail(v, ADDER_E_BAD_PARAMS, "null frame");
     PHIPCHK(v, hipSetDevice(v->p.device_id));
     const size_t fb = frame_bytes(v);
-    int rc = grow(v, &v->d_out, &v->d_out_cap, fb + 8u);
-    if (rc != ADDER_OK) return rc;
+    PHIPCHK(v, api_grow(&v->d_out, &v->d_out_cap, fb + 8u));
     PHIPCHK(v, player_display(v->a, v->d_out, v->stream));
     PHIPCHK(v, hipMemcpyAsync(frame, v->d_out, fb, hipMemcpyDeviceToHost, v->stream));
     PHIPCHK(v, hipStreamSynchronize(v->stream));

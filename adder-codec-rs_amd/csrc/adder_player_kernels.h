@@ -5,7 +5,6 @@
 
 namespace adder {
 
-enum PlayerSource : int { kPlayerEvents = 0, kPlayerWire9 = 1, kPlayerWire11 = 2 };
 
 struct PlayerScalars {  // device words of one call, read back once the schedule is known
     unsigned long long bad;    // smallest index of an event outside the plane (UINT64_MAX: none)

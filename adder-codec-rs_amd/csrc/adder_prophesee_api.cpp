@@ -6,15 +6,12 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <new>
-#include <string>
 #include <utility>
 #include <vector>
 
 #include "../../include/adder_prophesee.h"
+#include "adder_api_util.hpp"
 #include "adder_exp.hpp"
 #include "adder_log1p.hpp"
 #include "adder_prophesee_kernels.h"
@@ -77,24 +74,14 @@ struct AdderProphesee {
 };
 
 static int pfail(AdderProphesee *v, int code, const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    api_fail(v ? v->err : g_pph_create_error, code, fmt, ap);
     va_end(ap);
-    if (v)
-        v->err = buf;
-    else
-        g_pph_create_error = buf;
     return code;
 }
 
-#define PHIPCHK(v, expr)                                                                                        \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess)                                                                                   \
-            return pfail(v, ADDER_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#define PHIPCHK(v, expr) ADDER_HIPCHK(pfail, v, expr, #expr)
 
 // ------------------------------------------------------------------------------------------ header, records, groups
 extern "C" int adder_prophesee_parse_header(const uint8_t *b, size_t len, uint64_t file_size, AdderPropheseeHeader *out) {
@@ -214,9 +201,7 @@ extern "C" uint64_t adder_prophesee_scan_groups(const uint8_t *records, uint64_t
 
 // ------------------------------------------------------------------------------------------ lifecycle
 static void free_scratch(AdderProphesee *v) {
-    void *bufs[] = {v->s.keys0, v->s.keys1, v->s.idx0, v->s.idx1, v->s.cnt, v->s.offs, v->s.stage, v->s.temp};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    api_free_all({v->s.keys0, v->s.keys1, v->s.idx0, v->s.idx1, v->s.cnt, v->s.offs, v->s.stage, v->s.temp});
     PphScalars *sc = v->s.sc;
     v->s = PphScratch{};
     v->s.sc = sc;
@@ -229,10 +214,8 @@ static void pph_free(AdderProphesee *v) {
     if (v->stream) (void)hipStreamSynchronize(v->stream);
     (void)hipDeviceSynchronize();
     free_scratch(v);
-    void *bufs[] = {v->a.cur_t, v->a.nxt_t, v->a.cur_ln, v->a.nxt_ln, v->s.sc, v->pend,
-                    v->pend2,   v->steps,   v->d_in,     v->d_out};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    api_free_all({v->a.cur_t, v->a.nxt_t, v->a.cur_ln, v->a.nxt_ln, v->s.sc, v->pend, v->pend2, v->steps, v->d_in,
+                  v->d_out});
     if (v->h_sc) (void)hipHostFree(v->h_sc);
     if (v->h_t) (void)hipHostFree(v->h_t);
     if (v->ctx) adder_hip_destroy(v->ctx);
@@ -403,16 +386,6 @@ extern "C" int adder_prophesee_start(AdderProphesee *v, AdderEvent *out, uint64_
     return ADDER_OK;
 }
 
-static int grow(AdderProphesee *v, void **buf, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return ADDER_OK;
-    if (*buf) PHIPCHK(v, hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    PHIPCHK(v, hipMalloc(buf, bytes));
-    *cap = bytes;
-    return ADDER_OK;
-}
-
 static int ensure_steps(AdderProphesee *v, uint64_t n) {
     if (n <= v->steps_cap) return ADDER_OK;
     if (v->steps) PHIPCHK(v, hipFree(v->steps));
@@ -558,12 +531,11 @@ extern "C" int adder_prophesee_push_host(AdderProphesee *v, const uint8_t *recor
     // at most 2 steps per record in this push and the open group
     const uint64_t most = 2u * (v->pend_n + n) * v->eps;
     const uint64_t dcap = out_cap < most ? out_cap : most;
-    int rc = grow(v, &v->d_in, &v->d_in_cap, n * 8u + 8u);
-    if (rc == ADDER_OK) rc = grow(v, &v->d_out, &v->d_out_cap, dcap * sizeof(AdderEvent) + 16u);
-    if (rc != ADDER_OK) return rc;
+    PHIPCHK(v, api_grow(&v->d_in, &v->d_in_cap, n * 8u + 8u));
+    PHIPCHK(v, api_grow(&v->d_out, &v->d_out_cap, dcap * sizeof(AdderEvent) + 16u));
     if (n) PHIPCHK(v, hipMemcpyAsync(v->d_in, records, n * 8u, hipMemcpyHostToDevice, v->stream));
     uint64_t got = 0;
-    rc = push(v, n ? (const uint8_t *)v->d_in : nullptr, records, n, (AdderEvent *)v->d_out, dcap, &got, bad_index,
+    const int rc = push(v, n ? (const uint8_t *)v->d_in : nullptr, records, n, (AdderEvent *)v->d_out, dcap, &got, bad_index,
               v->stream);
     if (n_out) *n_out = got;
     if (rc == ADDER_OK && got) PHIPCHK(v, hipMemcpy(out, v->d_out, got * sizeof(AdderEvent), hipMemcpyDeviceToHost));
@@ -611,10 +583,9 @@ extern "C" int adder_prophesee_finish_host(AdderProphesee *v, AdderEvent *out, u
         return pfail(v, ADDER_E_OUT_CAPACITY, "end_events may make %llu events", (unsigned long long)need);
     }
     PHIPCHK(v, hipSetDevice(v->p.device_id));
-    int rc = grow(v, &v->d_out, &v->d_out_cap, need * sizeof(AdderEvent));
-    if (rc != ADDER_OK) return rc;
+    PHIPCHK(v, api_grow(&v->d_out, &v->d_out_cap, need * sizeof(AdderEvent)));
     uint64_t got = 0;
-    rc = adder_prophesee_finish_device(v, (AdderEvent *)v->d_out, need, &got, v->stream);
+    const int rc = adder_prophesee_finish_device(v, (AdderEvent *)v->d_out, need, &got, v->stream);
     if (rc != ADDER_OK) return rc;
     if (got) PHIPCHK(v, hipMemcpy(out, v->d_out, got * sizeof(AdderEvent), hipMemcpyDeviceToHost));
     if (n_out) *n_out = got;

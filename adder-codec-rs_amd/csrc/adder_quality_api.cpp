@@ -4,14 +4,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <limits>
 #include <new>
-#include <string>
 
 #include "../../include/adder_quality.h"
+#include "adder_api_util.hpp"
 #include "adder_quality_kernels.h"
 
 using namespace adder;
@@ -36,29 +33,17 @@ struct AdderQuality {
 };
 
 static int qfail(AdderQuality *q, int code, const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    api_fail(q ? q->err : g_quality_create_error, code, fmt, ap);
     va_end(ap);
-    if (q)
-        q->err = buf;
-    else
-        g_quality_create_error = buf;
     return code;
 }
 
-#define QHIPCHK(q, expr)                                                                                        \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess)                                                                                   \
-            return qfail(q, ADDER_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#define QHIPCHK(q, expr) ADDER_HIPCHK(qfail, q, expr, #expr)
 
 static void free_scratch(AdderQuality *q) {
-    if (q->sse_part) (void)hipFree(q->sse_part);
-    if (q->ssim_part) (void)hipFree(q->ssim_part);
-    if (q->d_sums) (void)hipFree(q->d_sums);
+    api_free_all({q->sse_part, q->ssim_part, q->d_sums});
     if (q->h_sums) (void)hipHostFree(q->h_sums);
     q->sse_part = nullptr;
     q->ssim_part = nullptr;
@@ -72,8 +57,7 @@ static void quality_free(AdderQuality *q) {
     (void)hipSetDevice(q->p.device_id);
     if (q->stream) (void)hipStreamSynchronize(q->stream);
     free_scratch(q);
-    if (q->d_in) (void)hipFree(q->d_in);
-    if (q->d_map) (void)hipFree(q->d_map);
+    api_free_all({q->d_in, q->d_map});
     if (q->stream) (void)hipStreamDestroy(q->stream);
     delete q;
 }
@@ -91,16 +75,6 @@ static int ensure_scratch(AdderQuality *q, uint32_t n) {
     QHIPCHK(q, hipMalloc((void **)&q->d_sums, (size_t)c * sizeof(QualityFrameSums)));
     QHIPCHK(q, hipHostMalloc((void **)&q->h_sums, (size_t)c * sizeof(QualityFrameSums), hipHostMallocDefault));
     q->cap = c;
-    return ADDER_OK;
-}
-
-static int grow(AdderQuality *q, void **buf, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return ADDER_OK;
-    if (*buf) QHIPCHK(q, hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    QHIPCHK(q, hipMalloc(buf, bytes));
-    *cap = bytes;
     return ADDER_OK;
 }
 
@@ -143,15 +117,7 @@ extern "C" int adder_quality_create(const AdderQualityParams *p, AdderQuality **
     const uint32_t all = ADDER_QUALITY_MSE | ADDER_QUALITY_PSNR | ADDER_QUALITY_SSIM;
     if (p->metrics == 0 || (p->metrics & ~all) != 0)
         return qfail(nullptr, ADDER_E_BAD_PARAMS, "metrics mask 0x%x (MSE 1 | PSNR 2 | SSIM 4, not empty)", p->metrics);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return qfail(nullptr, ADDER_E_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (p->device_id < 0 || p->device_id >= ndev)
-        return qfail(nullptr, ADDER_E_BAD_PARAMS, "device_id %d of %d", p->device_id, ndev);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device_id) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return qfail(nullptr, ADDER_E_NO_DEVICE, "device %d is not gfx950; this library is built for gfx950 only",
-                     p->device_id);
+    if (const int rc = api_check_device(p->device_id, g_quality_create_error)) return rc;
     AdderQuality *q = new (std::nothrow) AdderQuality();
     if (!q) return qfail(nullptr, ADDER_E_BAD_PARAMS, "out of host memory");
     q->p = *p;
@@ -212,10 +178,9 @@ extern "C" int adder_quality_compute_host(AdderQuality *q, const uint8_t *origin
     if (rc != ADDER_OK || n_frames == 0) return rc;
     QHIPCHK(q, hipSetDevice(q->p.device_id));
     const size_t bytes = (size_t)n_frames * q->s.frame_bytes;
-    rc = grow(q, (void **)&q->d_in, &q->d_in_cap, 2 * bytes);
+    QHIPCHK(q, api_grow((void **)&q->d_in, &q->d_in_cap, 2 * bytes));
     const size_t map_elems = ssim_map ? (size_t)adder_quality_map_elems(q, n_frames) : 0u;
-    if (rc == ADDER_OK && map_elems) rc = grow(q, (void **)&q->d_map, &q->d_map_cap, map_elems * sizeof(double));
-    if (rc != ADDER_OK) return rc;
+    if (map_elems) QHIPCHK(q, api_grow((void **)&q->d_map, &q->d_map_cap, map_elems * sizeof(double)));
     QHIPCHK(q, hipMemcpyAsync(q->d_in, original, bytes, hipMemcpyHostToDevice, q->stream));
     QHIPCHK(q, hipMemcpyAsync(q->d_in + bytes, reconstructed, bytes, hipMemcpyHostToDevice, q->stream));
     rc = compute(q, q->d_in, q->d_in + bytes, n_frames, out, map_elems ? q->d_map : nullptr, q->stream);

@@ -20,51 +20,25 @@
 
 #include "../../include/adder_stream.h"
 #include "adder_stream_kernels.h"
+#include "adder_wire.hpp"
 
 namespace adder {
 
-struct StreamEv {
-    uint32_t x, y, c, d, t;
-    bool end;  // EOF record or undecodable (raw/stream.rs:177-201: either ends the reading loop)
-};
-
-__device__ __forceinline__ uint32_t sbe16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
-__device__ __forceinline__ uint32_t sbe32(const uint8_t *p) {
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-// where the big-endian t sits in an 11-byte record: behind Some(c) (tag 1) or behind None (tag 0)
-__device__ __forceinline__ uint32_t wire11_t_offset(uint32_t tag) { return tag == 1u ? 7u : 6u; }
-
+// wire_load, but the 11-byte arm addresses d and t through wire11_t_offset, as stream_store does: the copy kernel loads
+// and stores the same record, and with one offset for both its wire-11 call measured 79 us against 85 us with the
+// branch of wire_load (1 << 22 records on 640x480x3; profiles/stream_wire11_timing.json).  Same result, byte for byte.
 template <int SRC>
-__device__ __forceinline__ StreamEv stream_load(const void *in, uint64_t i) {
-    StreamEv e;
-    e.end = false;
-    if (SRC == kStreamEvents) {
-        const AdderEvent ev = ((const AdderEvent *)in)[i];
-        e.x = ev.x;
-        e.y = ev.y;
-        e.c = ev.c == 0xffu ? 0u : ev.c;  // `c = None` counts as channel 0
-        e.d = ev.d;
-        e.t = ev.t;
-    } else if (SRC == kStreamWire9) {
-        const uint8_t *p = (const uint8_t *)in + i * 9u;
-        e.x = sbe16(p);
-        e.y = sbe16(p + 2);
-        e.c = 0u;
-        e.d = p[4];
-        e.t = sbe32(p + 5);
-        e.end = e.x == 0xffffu && e.y == 0xffffu;
-    } else {  // 11 bytes: x, y, Option<u8> c (bincode: tag byte, then the value when Some), d, t
-        const uint8_t *p = (const uint8_t *)in + i * 11u;
-        e.x = sbe16(p);
-        e.y = sbe16(p + 2);
-        const uint32_t tag = p[4];
-        e.c = tag == 1u ? p[5] : 0u;
-        e.d = p[wire11_t_offset(tag) - 1u];
-        e.t = sbe32(p + wire11_t_offset(tag));
-        e.end = tag > 1u || (e.x == 0xffffu && e.y == 0xffffu);
-    }
+__device__ __forceinline__ WireEv stream_load(const void *in, uint64_t i) {
+    if (SRC != kSrcWire11) return wire_load<SRC>(in, i);
+    const uint8_t *p = (const uint8_t *)in + i * 11u;
+    const uint32_t tag = p[4];
+    WireEv e;
+    e.x = wire_be16(p);
+    e.y = wire_be16(p + 2);
+    e.c = tag == 1u ? p[5] : 0u;
+    e.d = p[wire11_t_offset(tag) - 1u];
+    e.t = wire_be32(p + wire11_t_offset(tag));
+    e.end = tag > 1u || (e.x == 0xffffu && e.y == 0xffffu);
     return e;
 }
 
@@ -73,15 +47,15 @@ __device__ __forceinline__ StreamEv stream_load(const void *in, uint64_t i) {
 // byte 9 and its byte 10 is carried like the rest.
 template <int SRC>
 __device__ __forceinline__ void stream_store(const void *in, void *out, uint64_t i, uint32_t t) {
-    if (SRC == kStreamEvents) {
+    if (SRC == kSrcEvents) {
         AdderEvent ev = ((const AdderEvent *)in)[i];
         ev.t = t;
         ((AdderEvent *)out)[i] = ev;
     } else {
-        const uint32_t rb = SRC == kStreamWire9 ? 9u : 11u;
+        const uint32_t rb = SRC == kSrcWire9 ? 9u : 11u;
         const uint8_t *p = (const uint8_t *)in + i * rb;
         uint8_t *q = (uint8_t *)out + i * rb;
-        const uint32_t off = SRC == kStreamWire9 ? 5u : wire11_t_offset(p[4]);
+        const uint32_t off = SRC == kSrcWire9 ? 5u : wire11_t_offset(p[4]);
         if (q != p) {
             for (uint32_t k = 0; k < off; ++k) q[k] = p[k];
             for (uint32_t k = off + 4u; k < rb; ++k) q[k] = p[k];
@@ -91,14 +65,6 @@ __device__ __forceinline__ void stream_store(const void *in, void *out, uint64_t
         q[off + 2u] = (uint8_t)(t >> 8);
         q[off + 3u] = (uint8_t)t;
     }
-}
-
-__device__ __forceinline__ uint64_t stream_round_up(uint64_t t, uint64_t ref) {
-    return t % ref == 0u ? t : (t / ref + 1u) * ref;
-}
-
-__device__ __forceinline__ uint64_t stream_limit(const StreamScalars *sc) {
-    return sc->bad < sc->eof ? sc->bad : sc->eof;
 }
 
 __global__ void stream_init_kernel(StreamScalars *sc, uint64_t n) {
@@ -113,7 +79,7 @@ __global__ __launch_bounds__(256) void stream_keys_kernel(const void *__restrict
                                                           StreamScalars *sc) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const StreamEv e = stream_load<SRC>(in, i);
+    const WireEv e = stream_load<SRC>(in, i);
     uint32_t key = a.units;  // sorted behind every unit, never worked on
     if (e.end) {
         atomicMin(&sc->eof, (unsigned long long)i);
@@ -148,7 +114,7 @@ __global__ __launch_bounds__(256) void stream_forward_kernel(uint64_t n, StreamA
     if (j0 >= n) return;
     const uint32_t u = keys[j0];
     if (u >= a.units || (j0 > 0u && keys[j0 - 1] == u)) return;  // a thread per run of one unit
-    const uint64_t lim = stream_limit(sc);  // as the keys kernel left it; an overflow below can only lower it
+    const uint64_t lim = wire_limit(sc->bad, sc->eof);  // as the keys kernel left it; an overflow below can only lower it
     uint64_t T = a.state[u];
     for (uint64_t j = j0; j < n && keys[j] == u; ++j) {
         const uint32_t i = idx[j];
@@ -159,7 +125,7 @@ __global__ __launch_bounds__(256) void stream_forward_kernel(uint64_t n, StreamA
             break;
         }
         s_o[j] = (uint32_t)T;
-        if (a.round) T = stream_round_up(T, a.ref);
+        if (a.round) T = wire_round_up(T, a.ref);
     }
 }
 
@@ -178,7 +144,7 @@ __global__ __launch_bounds__(256) void stream_inverse_kernel(uint64_t n, StreamA
         L = a.state[u];
     } else {
         L = s_t[j - 1];
-        if (a.round) L = stream_round_up(L, a.ref);
+        if (a.round) L = wire_round_up(L, a.ref);
     }
     const uint64_t t = s_t[j];
     if (t < L)
@@ -200,7 +166,7 @@ __global__ __launch_bounds__(256) void stream_emit_kernel(const void *in, void *
     if (j >= n) return;
     const uint32_t u = keys[j];
     if (u >= a.units) return;
-    const uint64_t lim = stream_limit(sc);
+    const uint64_t lim = wire_limit(sc->bad, sc->eof);
     const uint32_t i = idx[j];
     if (i >= lim) return;
     const uint32_t o = s_o[j];
@@ -210,7 +176,7 @@ __global__ __launch_bounds__(256) void stream_emit_kernel(const void *in, void *
         dt[i] = o;
     if (j + 1u == n || keys[j + 1] != u || idx[j + 1] >= lim) {  // idx ascends within a run (stable sort)
         const uint64_t base = forward ? o : s_t[j];
-        a.state[u] = a.round ? stream_round_up(base, a.ref) : base;
+        a.state[u] = a.round ? wire_round_up(base, a.ref) : base;
     }
 }
 
@@ -218,7 +184,7 @@ template <int SRC>
 __global__ __launch_bounds__(256) void stream_copy_kernel(const void *in, void *out, uint64_t n,
                                                           const StreamScalars *sc) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i >= n || i >= stream_limit(sc)) return;
+    if (i >= n || i >= wire_limit(sc->bad, sc->eof)) return;
     stream_store<SRC>(in, out, i, stream_load<SRC>(in, i).t);
 }
 
@@ -252,8 +218,8 @@ __global__ __launch_bounds__(256) void stream_fold_prep_kernel(const void *__res
     f.v = __longlong_as_double(0x7ff0000000000000ll);  // min(m, +inf): the identity
     f.is_const = 0u;
     f.pad = 0u;
-    if (i < stream_limit(sc)) {
-        const StreamEv e = stream_load<SRC>(in, i);
+    if (i < wire_limit(sc->bad, sc->eof)) {
+        const WireEv e = stream_load<SRC>(in, i);
         const uint32_t t = dt ? dt[i] : e.t;
         if (e.d == 255u) {
             // D_EMPTY: ignored
@@ -277,7 +243,7 @@ __global__ __launch_bounds__(256) void stream_fold_map_kernel(uint64_t n, const 
     using Reduce = hipcub::BlockReduce<unsigned long long, 256>;
     __shared__ typename Reduce::TempStorage tmp;
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    const uint64_t lim = stream_limit(sc);
+    const uint64_t lim = wire_limit(sc->bad, sc->eof);
     unsigned long long cand = 0ull;
     if (i < n && i < lim) {
         const StreamMinOp f = op[i];
@@ -336,9 +302,9 @@ static hipError_t stream_migrate_src(const StreamArgs &a, int op, const void *in
 hipError_t stream_migrate(const StreamArgs &a, int op, int source, const void *in, void *out, uint64_t n,
                           const StreamScratch &s, hipStream_t stream) {
     if (n == 0u) return hipSuccess;
-    if (source == kStreamEvents) return stream_migrate_src<kStreamEvents>(a, op, in, out, n, s, stream);
-    if (source == kStreamWire9) return stream_migrate_src<kStreamWire9>(a, op, in, out, n, s, stream);
-    return stream_migrate_src<kStreamWire11>(a, op, in, out, n, s, stream);
+    if (source == kSrcEvents) return stream_migrate_src<kSrcEvents>(a, op, in, out, n, s, stream);
+    if (source == kSrcWire9) return stream_migrate_src<kSrcWire9>(a, op, in, out, n, s, stream);
+    return stream_migrate_src<kSrcWire11>(a, op, in, out, n, s, stream);
 }
 
 template <int SRC>
@@ -379,9 +345,9 @@ static hipError_t stream_info_src(const StreamArgs &a, int absolute, const void 
 hipError_t stream_info(const StreamArgs &a, int absolute, int source, const void *in, uint64_t n, double min0,
                        StreamFold *fold, const StreamScratch &s, hipStream_t stream) {
     if (n == 0u) return hipSuccess;
-    if (source == kStreamEvents) return stream_info_src<kStreamEvents>(a, absolute, in, n, min0, fold, s, stream);
-    if (source == kStreamWire9) return stream_info_src<kStreamWire9>(a, absolute, in, n, min0, fold, s, stream);
-    return stream_info_src<kStreamWire11>(a, absolute, in, n, min0, fold, s, stream);
+    if (source == kSrcEvents) return stream_info_src<kSrcEvents>(a, absolute, in, n, min0, fold, s, stream);
+    if (source == kSrcWire9) return stream_info_src<kSrcWire9>(a, absolute, in, n, min0, fold, s, stream);
+    return stream_info_src<kSrcWire11>(a, absolute, in, n, min0, fold, s, stream);
 }
 
 }  // namespace adder

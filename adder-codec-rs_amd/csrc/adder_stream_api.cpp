@@ -6,14 +6,12 @@
 #include <cfloat>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <new>
-#include <string>
 
 #include "../../include/adder_stream.h"
+#include "adder_api_util.hpp"
 #include "adder_stream_kernels.h"
+#include "adder_wire.hpp"
 
 using namespace adder;
 
@@ -37,32 +35,20 @@ struct AdderStream {
 };
 
 static int sfail(AdderStream *v, int code, const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    api_fail(v ? v->err : g_stream_create_error, code, fmt, ap);
     va_end(ap);
-    if (v)
-        v->err = buf;
-    else
-        g_stream_create_error = buf;
     return code;
 }
 
-#define SHIPCHK(v, expr)                                                                                        \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess)                                                                                   \
-            return sfail(v, ADDER_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#define SHIPCHK(v, expr) ADDER_HIPCHK(sfail, v, expr, #expr)
 
 static const StreamFold kEmptyFold = {DBL_MAX, 0ull, 0ull};
 
 static void free_scratch(AdderStream *v) {
-    void *bufs[] = {v->s.keys0, v->s.keys1, v->s.idx0, v->s.idx1, v->s.s_t, v->s.s_o, v->s.temp,
-                    v->s.dt,    v->s.op,    v->s.prefix};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    api_free_all({v->s.keys0, v->s.keys1, v->s.idx0, v->s.idx1, v->s.s_t, v->s.s_o, v->s.temp, v->s.dt, v->s.op,
+                  v->s.prefix});
     StreamScalars *sc = v->s.sc;
     v->s = StreamScratch{};
     v->s.sc = sc;
@@ -75,9 +61,7 @@ static void stream_free(AdderStream *v) {
     if (v->stream) (void)hipStreamSynchronize(v->stream);
     (void)hipDeviceSynchronize();
     free_scratch(v);
-    void *bufs[] = {v->a.state, v->info_t, v->s.sc, v->d_fold, v->d_in, v->d_out};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    api_free_all({v->a.state, v->info_t, v->s.sc, v->d_fold, v->d_in, v->d_out});
     if (v->h_sc) (void)hipHostFree(v->h_sc);
     if (v->h_fold) (void)hipHostFree(v->h_fold);
     if (v->stream) (void)hipStreamDestroy(v->stream);
@@ -108,20 +92,6 @@ static int ensure_scratch(AdderStream *v, uint64_t n, bool info) {
     return ADDER_OK;
 }
 
-static int grow(AdderStream *v, void **buf, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return ADDER_OK;
-    if (*buf) SHIPCHK(v, hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    SHIPCHK(v, hipMalloc(buf, bytes));
-    *cap = bytes;
-    return ADDER_OK;
-}
-
-static uint32_t rd16(const uint8_t *b) { return (uint32_t)((b[0] << 8) | b[1]); }
-static uint32_t rd32(const uint8_t *b) {
-    return ((uint32_t)b[0] << 24) | ((uint32_t)b[1] << 16) | ((uint32_t)b[2] << 8) | b[3];
-}
 static void wr32(uint8_t *b, uint32_t v) {
     b[0] = (uint8_t)(v >> 24);
     b[1] = (uint8_t)(v >> 16);
@@ -131,30 +101,24 @@ static void wr32(uint8_t *b, uint32_t v) {
 
 extern "C" int adder_stream_parse_header(const uint8_t *b, size_t len, AdderStreamParams *p, uint32_t *header_bytes,
                                          uint32_t *event_bytes) {
-    // header.rs:14-25 + encoder.rs:170-229: "adder", version, endianness 'b', u16 w, h, u32 tps, ref, delta_t_max,
-    // u8 event size, channels; then u32 source camera (v >= 1), time mode (v >= 2), adu interval (v >= 3), big-endian
-    if (!b || !p || len < 25 || memcmp(b, "adder", 5) != 0 || b[6] != 'b' || b[5] > 3) return ADDER_E_BAD_PARAMS;
-    const uint32_t version = b[5];
-    const uint32_t hdr = 25u + 4u * version;
-    if (len < hdr) return ADDER_E_BAD_PARAMS;
+    RawHeader h;
+    if (!p || !raw_header_parse(b, len, &h) || !raw_header_events_ok(h)) return ADDER_E_BAD_PARAMS;
+    if (h.time_mode > 2u) return ADDER_E_BAD_PARAMS;  // this tool rewrites the field: it has to know what it says
     AdderStreamParams q{};
     q.abi_version = ADDER_STREAM_ABI_VERSION;
-    q.width = (uint16_t)rd16(b + 7);
-    q.height = (uint16_t)rd16(b + 9);
-    q.tps = rd32(b + 11);
-    q.ref_interval = rd32(b + 15);
-    q.delta_t_max = rd32(b + 19);
-    const uint32_t esize = b[23];
-    q.channels = b[24];
-    q.codec_version = (uint8_t)version;
-    q.source_camera = version >= 1 ? rd32(b + 25) : 0u;
-    const uint32_t tm = version >= 2 ? rd32(b + 29) : 0u;
-    if (tm > 2u || q.channels == 0 || esize != (q.channels == 1 ? 9u : 11u)) return ADDER_E_BAD_PARAMS;
-    q.time_mode = q.out_time_mode = (uint8_t)tm;
+    q.width = (uint16_t)h.width;
+    q.height = (uint16_t)h.height;
+    q.tps = h.tps;
+    q.ref_interval = h.ref_interval;
+    q.delta_t_max = h.delta_t_max;
+    q.channels = (uint8_t)h.channels;
+    q.codec_version = (uint8_t)h.version;
+    q.source_camera = h.source_camera;
+    q.time_mode = q.out_time_mode = (uint8_t)h.time_mode;
     q.device_id = 0;
     *p = q;
-    if (header_bytes) *header_bytes = hdr;
-    if (event_bytes) *event_bytes = esize;
+    if (header_bytes) *header_bytes = h.header_bytes;
+    if (event_bytes) *event_bytes = h.event_size;
     return ADDER_OK;
 }
 
@@ -191,15 +155,7 @@ extern "C" int adder_stream_create(const AdderStreamParams *p, AdderStream **out
     if (p->codec_version > 3 || p->time_mode > 2 || p->out_time_mode > 2)
         return sfail(nullptr, ADDER_E_BAD_PARAMS, "codec version %u, time modes %u -> %u", p->codec_version,
                      p->time_mode, p->out_time_mode);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return sfail(nullptr, ADDER_E_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (p->device_id < 0 || p->device_id >= ndev)
-        return sfail(nullptr, ADDER_E_BAD_PARAMS, "device_id %d of %d", p->device_id, ndev);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p->device_id) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return sfail(nullptr, ADDER_E_NO_DEVICE, "device %d is not gfx950; this library is built for gfx950 only",
-                     p->device_id);
+    if (const int rc = api_check_device(p->device_id, g_stream_create_error)) return rc;
     AdderStream *v = new (std::nothrow) AdderStream();
     if (!v) return sfail(nullptr, ADDER_E_BAD_PARAMS, "out of host memory");
     v->p = *p;
@@ -270,9 +226,6 @@ extern "C" const char *adder_stream_last_error(const AdderStream *v) {
     return v ? v->err.c_str() : g_stream_create_error.c_str();
 }
 
-static int wire_source(const AdderStream *v) { return v->p.channels == 1 ? kStreamWire9 : kStreamWire11; }
-static size_t record_bytes(int source) { return source == kStreamEvents ? sizeof(AdderEvent) : source == kStreamWire9 ? 9u : 11u; }
-
 // d_out == nullptr: the info fold; otherwise the migration
 static int run(AdderStream *v, bool info, int source, const void *d_in, uint64_t n, void *d_out, uint64_t *bad_index,
                uint64_t *n_consumed, hipStream_t stream) {
@@ -310,25 +263,25 @@ static int run(AdderStream *v, bool info, int source, const void *d_in, uint64_t
 
 extern "C" int adder_stream_migrate_device(AdderStream *v, const AdderEvent *d_in, uint64_t n, AdderEvent *d_out,
                                            uint64_t *bad_index, void *stream) {
-    return run(v, false, kStreamEvents, d_in, n, d_out, bad_index, nullptr, (hipStream_t)stream);
+    return run(v, false, kSrcEvents, d_in, n, d_out, bad_index, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int adder_stream_migrate_wire_device(AdderStream *v, const uint8_t *d_wire, uint64_t n_records,
                                                 uint8_t *d_out, uint64_t *bad_index, uint64_t *n_consumed,
                                                 void *stream) {
     if (!v) return ADDER_E_BAD_PARAMS;
-    return run(v, false, wire_source(v), d_wire, n_records, d_out, bad_index, n_consumed, (hipStream_t)stream);
+    return run(v, false, wire_source(v->p.channels), d_wire, n_records, d_out, bad_index, n_consumed, (hipStream_t)stream);
 }
 
 extern "C" int adder_stream_info_device(AdderStream *v, const AdderEvent *d_events, uint64_t n, uint64_t *bad_index,
                                         void *stream) {
-    return run(v, true, kStreamEvents, d_events, n, nullptr, bad_index, nullptr, (hipStream_t)stream);
+    return run(v, true, kSrcEvents, d_events, n, nullptr, bad_index, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int adder_stream_info_wire_device(AdderStream *v, const uint8_t *d_wire, uint64_t n_records,
                                              uint64_t *bad_index, uint64_t *n_consumed, void *stream) {
     if (!v) return ADDER_E_BAD_PARAMS;
-    return run(v, true, wire_source(v), d_wire, n_records, nullptr, bad_index, n_consumed, (hipStream_t)stream);
+    return run(v, true, wire_source(v->p.channels), d_wire, n_records, nullptr, bad_index, n_consumed, (hipStream_t)stream);
 }
 
 static int run_host(AdderStream *v, bool info, int source, const void *in, uint64_t n, void *out, uint64_t *bad_index,
@@ -337,13 +290,11 @@ static int run_host(AdderStream *v, bool info, int source, const void *in, uint6
     if (n > (uint64_t)INT32_MAX) return sfail(v, ADDER_E_BAD_PARAMS, "too many events in one call");
     if (n > 0 && (!in || (!info && !out))) return sfail(v, ADDER_E_BAD_PARAMS, "null buffer");
     SHIPCHK(v, hipSetDevice(v->p.device_id));
-    const size_t rb = record_bytes(source);
-    int rc = grow(v, &v->d_in, &v->d_in_cap, n * rb + 1u);
-    if (rc == ADDER_OK && !info) rc = grow(v, &v->d_out, &v->d_out_cap, n * rb + 1u);
-    if (rc != ADDER_OK) return rc;
-    if (n) SHIPCHK(v, hipMemcpyAsync(v->d_in, in, n * rb, hipMemcpyHostToDevice, v->stream));
+    const size_t rb = wire_record_bytes(source);
+    if (!info) SHIPCHK(v, api_grow(&v->d_out, &v->d_out_cap, n * rb + 1u));
+    SHIPCHK(v, api_stage_input(&v->d_in, &v->d_in_cap, in, n * rb, v->stream));
     uint64_t bad = ADDER_STREAM_NO_BAD_EVENT, consumed = n;
-    rc = run(v, info, source, v->d_in, n, info ? nullptr : v->d_out, &bad, source == kStreamEvents ? nullptr : &consumed,
+    const int rc = run(v, info, source, v->d_in, n, info ? nullptr : v->d_out, &bad, source == kSrcEvents ? nullptr : &consumed,
              v->stream);
     if (bad_index) *bad_index = bad;
     if (n_consumed) *n_consumed = n ? consumed : 0;
@@ -356,23 +307,23 @@ static int run_host(AdderStream *v, bool info, int source, const void *in, uint6
 
 extern "C" int adder_stream_migrate_host(AdderStream *v, const AdderEvent *in, uint64_t n, AdderEvent *out,
                                          uint64_t *bad_index) {
-    return run_host(v, false, kStreamEvents, in, n, out, bad_index, nullptr);
+    return run_host(v, false, kSrcEvents, in, n, out, bad_index, nullptr);
 }
 
 extern "C" int adder_stream_migrate_wire_host(AdderStream *v, const uint8_t *wire, uint64_t n_records, uint8_t *out,
                                               uint64_t *bad_index, uint64_t *n_consumed) {
     if (!v) return ADDER_E_BAD_PARAMS;
-    return run_host(v, false, wire_source(v), wire, n_records, out, bad_index, n_consumed);
+    return run_host(v, false, wire_source(v->p.channels), wire, n_records, out, bad_index, n_consumed);
 }
 
 extern "C" int adder_stream_info_host(AdderStream *v, const AdderEvent *events, uint64_t n, uint64_t *bad_index) {
-    return run_host(v, true, kStreamEvents, events, n, nullptr, bad_index, nullptr);
+    return run_host(v, true, kSrcEvents, events, n, nullptr, bad_index, nullptr);
 }
 
 extern "C" int adder_stream_info_wire_host(AdderStream *v, const uint8_t *wire, uint64_t n_records, uint64_t *bad_index,
                                            uint64_t *n_consumed) {
     if (!v) return ADDER_E_BAD_PARAMS;
-    return run_host(v, true, wire_source(v), wire, n_records, nullptr, bad_index, n_consumed);
+    return run_host(v, true, wire_source(v->p.channels), wire, n_records, nullptr, bad_index, n_consumed);
 }
 
 extern "C" int adder_stream_info_range(const AdderStream *v, double *min_intensity, double *max_intensity,

@@ -5,7 +5,6 @@
 
 namespace adder {
 
-enum StreamSource : int { kStreamEvents = 0, kStreamWire9 = 1, kStreamWire11 = 2 };
 enum StreamOp : int { kStreamPass = 0, kStreamForward = 1, kStreamInverse = 2 };
 
 struct StreamScalars {  // device words of one call, read back once at its end

@@ -21,58 +21,9 @@
 #include "../../include/adder_viz_player.h"
 #include "adder_viz_player_kernels.h"
 #include "adder_viz_player_logic.hpp"
+#include "adder_wire.hpp"
 
 namespace adder {
-
-struct VizEv {
-    uint32_t x, y, c, d, t;
-    bool end;  // EOF record or undecodable
-};
-
-__device__ __forceinline__ uint32_t vz_be16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
-__device__ __forceinline__ uint32_t vz_be32(const uint8_t *p) {
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-template <int SRC>
-__device__ __forceinline__ VizEv viz_load(const void *in, uint64_t i) {
-    VizEv e;
-    e.end = false;
-    if (SRC == kVizEvents) {
-        const AdderEvent ev = ((const AdderEvent *)in)[i];
-        e.x = ev.x;
-        e.y = ev.y;
-        e.c = ev.c == 0xffu ? 0u : ev.c;  // `c = None` counts as channel 0
-        e.d = ev.d;
-        e.t = ev.t;
-    } else if (SRC == kVizWire9) {
-        const uint8_t *p = (const uint8_t *)in + i * 9u;
-        e.x = vz_be16(p);
-        e.y = vz_be16(p + 2);
-        e.c = 0u;
-        e.d = p[4];
-        e.t = vz_be32(p + 5);
-        e.end = e.x == 0xffffu && e.y == 0xffffu;
-    } else {  // 11 bytes: x, y, Option<u8> c (tag byte, then the value when Some), d, t
-        const uint8_t *p = (const uint8_t *)in + i * 11u;
-        e.x = vz_be16(p);
-        e.y = vz_be16(p + 2);
-        const uint32_t tag = p[4];
-        if (tag == 1u) {
-            e.c = p[5];
-            e.d = p[6];
-            e.t = vz_be32(p + 7);
-        } else {
-            e.c = 0u;
-            e.d = p[5];
-            e.t = vz_be32(p + 6);
-        }
-        e.end = tag > 1u || (e.x == 0xffffu && e.y == 0xffffu);
-    }
-    return e;
-}
-
-__device__ __forceinline__ uint64_t viz_lim(const VizScalars *sc) { return sc->bad < sc->eof ? sc->bad : sc->eof; }
 
 __global__ void viz_init_kernel(VizScalars *sc, uint64_t n) {
     sc->bad = ~0ull;
@@ -91,7 +42,7 @@ __global__ __launch_bounds__(256) void viz_keys_kernel(const void *__restrict__ 
                                                        int32_t *__restrict__ l_in, VizScalars *sc) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const VizEv e = viz_load<SRC>(in, i);
+    const WireEv e = wire_load<SRC>(in, i);
     uint32_t uk = a.units, rk = a.height;
     if (e.end) {
         atomicMin(&sc->eof, (unsigned long long)i);
@@ -119,14 +70,14 @@ __global__ __launch_bounds__(256) void viz_walk_kernel(const void *__restrict__ 
     if (j0 >= n) return;
     const uint32_t u = ukeys[j0];
     if (u >= a.units || (j0 > 0u && ukeys[j0 - 1] == u)) return;
-    const uint64_t lim = viz_lim(sc);
+    const uint64_t lim = wire_limit(sc->bad, sc->eof);
     FramerPx p = a.px[u];
     bool overflow = false, deep = false;
     const int64_t past_ring = (int64_t)w0 + (int64_t)a.ring;
     for (uint64_t j = j0; j < n && ukeys[j] == u; ++j) {
         const uint32_t i = uidx[j];
         if (i >= lim) break;
-        const VizEv e = viz_load<SRC>(in, i);
+        const WireEv e = wire_load<SRC>(in, i);
         const bool checked = !(a.k.abs_t && p.ts >= (uint64_t)e.t);
         int32_t from = 0, to = 0;
         if (framer_step(p, e.d, e.t, a.k, from, to, overflow) && (int64_t)to >= past_ring) deep = true;
@@ -157,7 +108,7 @@ __global__ __launch_bounds__(256) void viz_coverage_kernel(uint64_t n, VizArgs a
     const uint32_t u = ukeys[j];
     if (u >= a.units) return;
     const uint32_t i = uidx[j];
-    if (i >= viz_lim(sc)) return;
+    if (i >= wire_limit(sc->bad, sc->eof)) return;
     int32_t from, to;
     viz_range(a, j, u, ukeys, s_l, from, to);
     const uint32_t r = u / a.row_units;
@@ -223,7 +174,7 @@ struct VizBlockRows {
 __global__ __launch_bounds__(256) void viz_schedule_kernel(VizSchedIn v, int32_t *pops, uint8_t *flushed, uint8_t *done,
                                                            VizScalars *sc) {
     __shared__ long long sh[256];
-    v.n = (int64_t)viz_lim(sc);
+    v.n = (int64_t)wire_limit(sc->bad, sc->eof);
     VizSchedOut o;
     o.pops = pops;
     o.flushed = flushed;
@@ -413,9 +364,9 @@ static hipError_t viz_prepare_src(const VizArgs &a, const void *in, uint64_t n, 
 
 hipError_t viz_prepare(const VizArgs &a, int source, const void *in, uint64_t n, int32_t w0, int32_t m0, int has_limit,
                        uint32_t limit, int opening, int finish, VizScratch &s, hipStream_t stream) {
-    if (source == kVizEvents) return viz_prepare_src<kVizEvents>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, stream);
-    if (source == kVizWire9) return viz_prepare_src<kVizWire9>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, stream);
-    return viz_prepare_src<kVizWire11>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, stream);
+    if (source == kSrcEvents) return viz_prepare_src<kSrcEvents>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, stream);
+    if (source == kSrcWire9) return viz_prepare_src<kSrcWire9>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, stream);
+    return viz_prepare_src<kSrcWire11>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, stream);
 }
 
 hipError_t viz_handout_commit(const VizArgs &a, uint64_t n, uint64_t lim, int32_t w0, uint32_t n_pops, int form,

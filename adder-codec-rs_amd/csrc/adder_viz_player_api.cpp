@@ -5,17 +5,15 @@
 
 #include <algorithm>
 #include <climits>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <new>
 #include <numeric>
-#include <string>
 #include <vector>
 
 #include "../../include/adder_viz_player.h"
+#include "adder_api_util.hpp"
 #include "adder_viz_player_kernels.h"
 #include "adder_viz_player_logic.hpp"
+#include "adder_wire.hpp"
 
 using namespace adder;
 
@@ -45,31 +43,19 @@ struct AdderVizPlayer {
 };
 
 static int vfail(AdderVizPlayer *v, int code, const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    api_fail(v ? v->err : g_viz_create_error, code, fmt, ap);
     va_end(ap);
-    if (v)
-        v->err = buf;
-    else
-        g_viz_create_error = buf;
     return code;
 }
 
-#define VHIPCHK(v, expr)                                                                                        \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess)                                                                                   \
-            return vfail(v, ADDER_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#define VHIPCHK(v, expr) ADDER_HIPCHK(vfail, v, expr, #expr)
 
 static void free_scratch(AdderVizPlayer *v) {
     VizScratch &s = v->s;
-    void *bufs[] = {s.ukeys0, s.ukeys1, s.uidx0, s.uidx1, s.rkeys0, s.rkeys1, s.ridx0,  s.ridx1,
-                    s.s_l,    s.s_val,  s.s_px,  s.l_in,  s.pm,     s.comb_in, s.comb, s.temp};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    api_free_all({s.ukeys0, s.ukeys1, s.uidx0, s.uidx1, s.rkeys0, s.rkeys1, s.ridx0, s.ridx1, s.s_l, s.s_val, s.s_px, s.l_in,
+                  s.pm, s.comb_in, s.comb, s.temp});
     VizScratch keep{};
     keep.cnt_call = s.cnt_call;
     keep.nat_call = s.nat_call;
@@ -87,10 +73,8 @@ static void viz_free(AdderVizPlayer *v) {
     if (v->stream) (void)hipStreamSynchronize(v->stream);
     (void)hipDeviceSynchronize();
     free_scratch(v);
-    void *bufs[] = {v->a.px,       v->a.ring_val, v->a.ring_some, v->a.running, v->a.cnt,  v->a.done, v->a.run_lo,
-                    v->s.cnt_call, v->s.nat_call, v->s.done_new,  v->s.pops,    v->s.flushed, v->s.sc, v->d_in, v->d_out};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    api_free_all({v->a.px, v->a.ring_val, v->a.ring_some, v->a.running, v->a.cnt, v->a.done, v->a.run_lo, v->s.cnt_call,
+                  v->s.nat_call, v->s.done_new, v->s.pops, v->s.flushed, v->s.sc, v->d_in, v->d_out});
     if (v->h_sc) (void)hipHostFree(v->h_sc);
     if (v->h_pops) (void)hipHostFree(v->h_pops);
     if (v->stream) (void)hipStreamDestroy(v->stream);
@@ -121,16 +105,6 @@ static int ensure_scratch(AdderVizPlayer *v, uint64_t n) {
     s.temp_bytes = viz_temp_bytes(c);
     VHIPCHK(v, hipMalloc(&s.temp, s.temp_bytes));
     v->cap = c;
-    return ADDER_OK;
-}
-
-static int grow(AdderVizPlayer *v, void **buf, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return ADDER_OK;
-    if (*buf) VHIPCHK(v, hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    VHIPCHK(v, hipMalloc(buf, bytes));
-    *cap = bytes;
     return ADDER_OK;
 }
 
@@ -182,15 +156,7 @@ extern "C" int adder_viz_player_create(const AdderVizPlayerParams *pp, AdderVizP
     if (ring > (1u << 16) || ring * p.height >= (1ull << 31))
         return vfail(nullptr, ADDER_E_BAD_PARAMS, "ring_frames %llu (at most 65536, and height * ring_frames < 2^31)",
                      (unsigned long long)ring);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return vfail(nullptr, ADDER_E_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (p.device_id < 0 || p.device_id >= ndev)
-        return vfail(nullptr, ADDER_E_BAD_PARAMS, "device_id %d of %d", p.device_id, ndev);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, p.device_id) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return vfail(nullptr, ADDER_E_NO_DEVICE, "device %d is not gfx950; this library is built for gfx950 only",
-                     p.device_id);
+    if (const int rc = api_check_device(p.device_id, g_viz_create_error)) return rc;
     AdderVizPlayer *v = new (std::nothrow) AdderVizPlayer();
     if (!v) return vfail(nullptr, ADDER_E_BAD_PARAMS, "out of host memory");
     v->p = p;
@@ -301,8 +267,7 @@ static int run(AdderVizPlayer *v, int source, const void *d_in, uint64_t n, int 
         return vfail(v, ADDER_E_OUT_CAPACITY, "%u frames do not fit in %llu", sc.n_pops, (unsigned long long)frame_cap);
     const size_t fb = a.units;
     if (h_frames) {
-        rc = grow(v, &v->d_out, &v->d_out_cap, (size_t)sc.n_pops * fb + 8u);
-        if (rc != ADDER_OK) return rc;
+        VHIPCHK(v, api_grow(&v->d_out, &v->d_out_cap, (size_t)sc.n_pops * fb + 8u));
         d_frames = (uint8_t *)v->d_out;
     }
     VHIPCHK(v, viz_handout_commit(a, n, lim, v->frames_written, sc.n_pops, form, d_frames, v->s, stream));
@@ -325,12 +290,10 @@ static int run(AdderVizPlayer *v, int source, const void *d_in, uint64_t n, int 
     return ADDER_OK;
 }
 
-static int wire_source(const AdderVizPlayer *v) { return v->p.channels == 1 ? kVizWire9 : kVizWire11; }
-
 extern "C" int adder_viz_player_ingest_device(AdderVizPlayer *v, const AdderEvent *d_events, uint64_t n, int form,
                                               uint8_t *d_frames, uint64_t frame_cap, uint64_t *n_frames,
                                               int64_t *pop_index, uint64_t *bad_index, void *stream) {
-    return run(v, kVizEvents, d_events, n, 0, form, d_frames, nullptr, frame_cap, n_frames, pop_index, bad_index, nullptr,
+    return run(v, kSrcEvents, d_events, n, 0, form, d_frames, nullptr, frame_cap, n_frames, pop_index, bad_index, nullptr,
                (hipStream_t)stream);
 }
 
@@ -339,19 +302,19 @@ extern "C" int adder_viz_player_ingest_wire_device(AdderVizPlayer *v, const uint
                                                    int64_t *pop_index, uint64_t *bad_index, uint64_t *n_consumed,
                                                    void *stream) {
     if (!v) return ADDER_E_BAD_PARAMS;
-    return run(v, wire_source(v), d_wire, n_records, 0, form, d_frames, nullptr, frame_cap, n_frames, pop_index,
-               bad_index, n_consumed, (hipStream_t)stream);
+    return run(v, wire_source(v->p.channels), d_wire, n_records, 0, form, d_frames, nullptr, frame_cap, n_frames,
+               pop_index, bad_index, n_consumed, (hipStream_t)stream);
 }
 
 extern "C" int adder_viz_player_finish_device(AdderVizPlayer *v, int form, uint8_t *d_frames, uint64_t frame_cap,
                                               uint64_t *n_frames, int64_t *pop_index, void *stream) {
-    return run(v, kVizEvents, nullptr, 0, 1, form, d_frames, nullptr, frame_cap, n_frames, pop_index, nullptr, nullptr,
+    return run(v, kSrcEvents, nullptr, 0, 1, form, d_frames, nullptr, frame_cap, n_frames, pop_index, nullptr, nullptr,
                (hipStream_t)stream);
 }
 
 static uint8_t g_none;  // a non-null host target for a capacity of zero
 
-static int run_host(AdderVizPlayer *v, int source, const void *in, uint64_t n, size_t in_rec, int form, uint8_t *frames,
+static int run_host(AdderVizPlayer *v, int source, const void *in, uint64_t n, int form, uint8_t *frames,
                     uint64_t frame_cap, uint64_t *n_frames, int64_t *pop_index, uint64_t *bad_index,
                     uint64_t *n_consumed) {
     if (!v) return ADDER_E_BAD_PARAMS;
@@ -359,32 +322,29 @@ static int run_host(AdderVizPlayer *v, int source, const void *in, uint64_t n, s
     if (n > 0 && !in) return vfail(v, ADDER_E_BAD_PARAMS, "null input");
     if (frame_cap > 0 && !frames) return vfail(v, ADDER_E_BAD_PARAMS, "null frames");
     VHIPCHK(v, hipSetDevice(v->p.device_id));
-    int rc = grow(v, &v->d_in, &v->d_in_cap, n * in_rec + 1u);
-    if (rc != ADDER_OK) return rc;
-    if (n) VHIPCHK(v, hipMemcpyAsync(v->d_in, in, n * in_rec, hipMemcpyHostToDevice, v->stream));
+    VHIPCHK(v, api_stage_input(&v->d_in, &v->d_in_cap, in, n * wire_record_bytes(source), v->stream));
     return run(v, source, v->d_in, n, 0, form, nullptr, frames ? frames : &g_none, frame_cap, n_frames, pop_index,
                bad_index, n_consumed, v->stream);
 }
 
 extern "C" int adder_viz_player_ingest(AdderVizPlayer *v, const AdderEvent *events, uint64_t n, int form, uint8_t *frames,
                                        uint64_t frame_cap, uint64_t *n_frames, int64_t *pop_index, uint64_t *bad_index) {
-    return run_host(v, kVizEvents, events, n, sizeof(AdderEvent), form, frames, frame_cap, n_frames, pop_index, bad_index,
-                    nullptr);
+    return run_host(v, kSrcEvents, events, n, form, frames, frame_cap, n_frames, pop_index, bad_index, nullptr);
 }
 
 extern "C" int adder_viz_player_ingest_wire(AdderVizPlayer *v, const uint8_t *wire, uint64_t n_records, int form,
                                             uint8_t *frames, uint64_t frame_cap, uint64_t *n_frames, int64_t *pop_index,
                                             uint64_t *bad_index, uint64_t *n_consumed) {
     if (!v) return ADDER_E_BAD_PARAMS;
-    return run_host(v, wire_source(v), wire, n_records, v->p.channels == 1 ? 9u : 11u, form, frames, frame_cap, n_frames,
-                    pop_index, bad_index, n_consumed);
+    return run_host(v, wire_source(v->p.channels), wire, n_records, form, frames, frame_cap, n_frames, pop_index,
+                    bad_index, n_consumed);
 }
 
 extern "C" int adder_viz_player_finish(AdderVizPlayer *v, int form, uint8_t *frames, uint64_t frame_cap,
                                        uint64_t *n_frames, int64_t *pop_index) {
     if (!v) return ADDER_E_BAD_PARAMS;
     if (frame_cap > 0 && !frames) return vfail(v, ADDER_E_BAD_PARAMS, "null frames");
-    return run(v, kVizEvents, nullptr, 0, 1, form, nullptr, frames ? frames : &g_none, frame_cap, n_frames, pop_index,
+    return run(v, kSrcEvents, nullptr, 0, 1, form, nullptr, frames ? frames : &g_none, frame_cap, n_frames, pop_index,
                nullptr, nullptr, v->stream);
 }
 

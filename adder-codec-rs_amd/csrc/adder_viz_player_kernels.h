@@ -8,7 +8,6 @@
 
 namespace adder {
 
-enum VizSource : int { kVizEvents = 0, kVizWire9 = 1, kVizWire11 = 2 };
 enum : uint32_t { kVizStatusRange = 1u, kVizStatusDepth = 2u };
 
 struct VizScalars {  // device words of one call, read back once the schedule is known
