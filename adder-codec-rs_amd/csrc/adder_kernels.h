@@ -1,4 +1,4 @@
-// adder_kernels.h -- launch interface between the C-ABI (adder_hip_api.cpp) and the
+// adder_kernels.h -- launch interface between the C-ABI (the adder_hip_*.cpp files) and the
 // gfx950 kernels (adder_kernels.hip).  Internal; the public boundary is include/adder_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -3621,7 +3621,7 @@ __global__ void adder_synth_kernel(uint8_t *dst, int content, uint64_t seed, uin
 
 }  // namespace adder
 
-// ------------------------- launch wrappers (called from adder_hip_api.cpp) -------------------------
+// ------------------------- launch wrappers (called from the adder_hip_*.cpp files) -------------------------
 using namespace adder;
 
 // Exhaustive check of fdiv_small against the IEEE division on its whole domain

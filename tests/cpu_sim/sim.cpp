@@ -262,7 +262,7 @@ int sim_integrate_sparse(Sim *s, const SimSparseStep *steps, size_t n, SimEvent 
     return rc;
 }
 
-// the product's choice (adder_hip_api.cpp cb_possible): Collapse, delta_t_max > time_spanned, uniform c_thresh, and
+// the product's choice (adder_batch_plan.hpp cb_possible): Collapse, delta_t_max > time_spanned, uniform c_thresh, and
 // every sum the prefix coordinates form an exact integer below 2^24
 static bool sim_cb_possible(const Sim *s, float T) {
     if (!s->use_cb || !s->collapse || s->perpx || s->continuous || s->frac_time_seen) return false;
@@ -822,9 +822,9 @@ int sim_integrate(Sim *s, const uint8_t *frame, float time_spanned, SimEvent *ou
     sc.abs_t = s->abs_t;
     sc.max_depth = s->max_depth;
     sc.ref_magic = s->ref_time >= 2 ? (uint32_t)(0x100000000ull / s->ref_time) : 0u;
-    // the product's variant choice (adder_hip_api.cpp enqueue_frames): lean iff Collapse with
+    // the product's variant choice (adder_hip_batch.cpp enqueue_frames): lean iff Collapse with
     // delta_t_max <= time_spanned and no generic batch has run since the last reset
-    // feature path (adder_hip_api.cpp prepare_per_unit_c_thresh): one pair per unit from the first frame that can
+    // feature path (adder_hip_batch.cpp prepare_per_unit_c_thresh): one pair per unit from the first frame that can
     // make them differ
     const bool needs_perpx = s->roi_on || (s->feat_detect && s->feat_adjust && s->radius > 0);
     if (needs_perpx && !s->perpx) {

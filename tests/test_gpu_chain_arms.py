@@ -25,7 +25,7 @@ def _start_up_frames_without_a_captured_graph(monkeypatch):
     """These tests open well over a hundred Prophesee contexts, each with an inner dense context whose two start-up
     frames would instantiate a captured graph that dies with the context.  This HIP runtime is known to crash in a
     later hipGraphLaunch of another instance once many instances have been destroyed in the process
-    (csrc/adder_hip_api.cpp, retired_execs), so the contexts of this module launch their start-up frames eagerly
+    (csrc/adder_hip_ctx.hpp, retired_execs), so the contexts of this module launch their start-up frames eagerly
     (read at create): the chain kernels under test and the sparse integrator take no graph either way, and the
     start-up frames through their graph are tests/test_gpu_prophesee.py's."""
     monkeypatch.setenv("ADDER_HIP_NO_GRAPH", "1")

@@ -74,5 +74,7 @@ int main() {
 }
 // Build and run from adder-codec-rs_amd/ after `make` (the other objects stay as they are):
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//       -x hip csrc/adder_hip_api.cpp -x c++ host/adder_host.cpp host/adder_host_c.cpp ../tools/sanitize/live_view_args.cpp \
-//       -x none $(ls obj/*.o | grep -v adder_hip_api) -fsanitize=address,undefined -o /tmp/live_view_args && /tmp/live_view_args
+//       -x hip csrc/adder_hip_api.cpp csrc/adder_hip_batch.cpp csrc/adder_hip_graphs.cpp csrc/adder_hip_ring_api.cpp \
+//       csrc/adder_hip_records_api.cpp csrc/adder_hip_features_api.cpp csrc/adder_hip_sparse_api.cpp \
+//       -x c++ host/adder_host.cpp host/adder_host_c.cpp ../tools/sanitize/live_view_args.cpp \
+//       -x none $(ls obj/*.o | grep -v 'obj/adder_hip_') -fsanitize=address,undefined -o /tmp/live_view_args && /tmp/live_view_args
