@@ -46,6 +46,7 @@ static void free_ctx(AdderHipCtx *c) {
                     c->snap.cn_integ, c->snap.cn_dt, c->snap.cn_bdt, c->snap.cn_meta,
                     c->d_offsets, c->d_frames, c->d_events, c->d_chunks, c->d_wire,
                     c->cth_px, c->cctr_px, c->fset, c->fstamp, c->d_display, c->own.feat_counters, c->snap.cth_px, c->snap.cctr_px, c->snap.fset,
+                    c->snap.fstamp,
                     c->snap.running};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);

@@ -359,6 +359,7 @@ static int take_snapshot(AdderHipCtx *c, bool deep, hipStream_t s) {
         HIPCHK(c, snap_copy(&n.cctr_px, c->cctr_px, c->n_pad, s));
     }
     if (c->fset) HIPCHK(c, snap_copy(&n.fset, c->fset, (size_t)c->rows * c->p.width, s));
+    if (c->fstamp) HIPCHK(c, snap_copy(&n.fstamp, c->fstamp, (size_t)c->rows * c->p.width, s));
     n.has_running = c->running != nullptr;
     if (c->running) HIPCHK(c, snap_copy(&n.running, c->running, c->n_pad, s));
     snapshot_scalars(c);
@@ -421,6 +422,9 @@ int restore_snapshot(AdderHipCtx *c, hipStream_t s) {
         HIPCHK(c, hipMemcpyAsync(c->cctr_px, n.cctr_px, c->n_pad, hipMemcpyDeviceToDevice, s));
     }
     if (!n.lean2 && c->fset && n.fset) HIPCHK(c, hipMemcpyAsync(c->fset, n.fset, (size_t)c->rows * c->p.width, hipMemcpyDeviceToDevice, s));
+    // (the display's Instant mode reads the stamps alone: none may stay above the restored frames_done)
+    if (!n.lean2 && c->fstamp && n.fstamp)
+        HIPCHK(c, hipMemcpyAsync(c->fstamp, n.fstamp, (size_t)c->rows * c->p.width * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     c->perpx = n.perpx;
     if (c->running && n.has_running) HIPCHK(c, hipMemcpyAsync(c->running, n.running, c->n_pad, hipMemcpyDeviceToDevice, s));
     HIPCHK(c, hipMemsetAsync(c->status, 0, sizeof(uint32_t), s));

@@ -89,6 +89,7 @@ struct AdderHipCtx {
         uint64_t frames_done = 0, run_bound = 0;
         bool generic_sticky = false;
         uint8_t *cth_px = nullptr, *cctr_px = nullptr, *fset = nullptr, *running = nullptr;
+        uint32_t *fstamp = nullptr;  // beside fset: a refused batch's stamps lie above the restored frames_done
         bool perpx = false, has_running = false;
     } snap;
     // feature-driven rate control + ROI (video.rs:825-837, 865-1112, 1291-1293)

@@ -1,4 +1,4 @@
-"""The launch-geometry constants of the quality, framer and stream hand-off kernels, read from their headers, so the edge tests take
+"""The launch-geometry constants of the quality, framer, stream hand-off and display kernels, read from their sources, so the edge tests take
 their shapes from the values the kernels are built with: a retune moves the tests with it.  A name that is missing, or
 an expression this cannot evaluate, raises."""
 import os
@@ -10,6 +10,7 @@ CSRC = os.path.join(ROOT, "adder-codec-rs_amd", "csrc")
 QUALITY_NAMES = ("kQualBlock", "kSsimTileW", "kSsimTileH", "kSseBytesPerBlock", "kSseMaxBlocks")
 FRAMER_NAMES = ("kFramerPopMaxBlocks", "kFramerPopUnitsPerBlock", "kFramerPopWideUnitsPerBlock",
                 "kFramerMinmaxMaxBlocks", "kFramerMinmaxUnitsPerBlock")
+DISPLAY_NAMES = ("kDisplayRows", "kDisplayTileBytes")
 HANDOFF_NAMES = ("kBlockThreads", "kWireEvents", "kScatterGroupsPerCu", "kMergeTileFrames", "kMaxGridRows")
 
 _DECL = re.compile(r"^\s*constexpr\s+uint32_t\s+(\w+)\s*=\s*([^;]+);", re.M)
@@ -46,3 +47,7 @@ def framer():
 
 def handoff():
     return _read("adder_kernels.h", HANDOFF_NAMES)
+
+
+def display():
+    return _read("adder_display.hip", DISPLAY_NAMES)
