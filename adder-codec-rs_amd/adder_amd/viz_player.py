@@ -63,6 +63,13 @@ SYMBOLS = {
     "adder_viz_player_ingest_wire": (_i32, [_vp, _vp, _u64, _i32, _vp, _u64, _pu64, _vp, _pu64, _pu64]),
     "adder_viz_player_finish": (_i32, [_vp, _i32, _vp, _u64, _pu64, _vp]),
     "adder_viz_player_running_frame": (_i32, [_vp, _vp]),
+    "adder_viz_player_detect_features": (_i32, [_vp, _i32]),
+    "adder_viz_player_features": (_i32, [_vp, _vp, _u64, _pu64]),
+    "adder_viz_player_frame_features": (_i32, [_vp, _vp, _vp, _vp, _u64, _pu64]),
+    "adder_viz_player_running_intensities": (_i32, [_vp, _vp]),
+    "adder_viz_player_running_intensities_device": (_i32, [_vp, _vp, _vp]),
+    "adder_viz_features_host": (_i32, [_vp, _u32, _u64, _vp, _i32, _vp, _vp]),
+    "adder_viz_overlay_host": (_i32, [_u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp]),
     "adder_viz_schedule_host": (C.c_int64, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _i32, _u32, _i32, _vp, _vp, _u64]),
 }
 
@@ -85,6 +92,37 @@ def schedule_host(row, frm, to, last_filled, rows, row_units, buffer_limit, fini
     if k < 0:
         raise ValueError("adder_viz_schedule_host refused its arguments")
     return pops[:k], fl[:k]
+
+
+def features_host(pops, marks, w0=0):
+    """Where the schedule meets detection, on the host (the functions the kernels run): pops = the local index of the
+    event after which each frame is popped, marks = FAST corners per event -> (marks without the first event of every
+    period, uint8; frames_written of each event's period, int32)."""
+    pops = np.ascontiguousarray(pops, dtype=np.int32)
+    marks = np.ascontiguousarray(marks, dtype=np.uint8)
+    out, w = np.zeros(len(marks), np.uint8), np.zeros(len(marks), np.int32)
+    rc = load().adder_viz_features_host(pops.ctypes.data if len(pops) else None, len(pops), len(marks),
+                                        marks.ctypes.data, w0, out.ctypes.data, w.ctypes.data)
+    if rc != N.OK:
+        raise ValueError("adder_viz_features_host refused its arguments")
+    return out, w
+
+
+def overlay_host(some, val, stamps, running):
+    """The hand-out's running-frame rule on the host: some / val [n_pops, units] (the popped frames), stamps = (unit,
+    frame k) pairs in any order, running = the running frame before -> (RUNNING-form frames, the running frame after)."""
+    some = np.ascontiguousarray(some, dtype=np.uint8)
+    val = np.ascontiguousarray(val, dtype=np.uint8)
+    n_pops, units = some.shape
+    keys = np.sort(np.array([(int(u) << 32) | int(k) for u, k in stamps], np.uint64))
+    run = np.array(running, np.uint8).reshape(-1).copy()
+    frames = np.zeros((n_pops, units), np.uint8)
+    rc = load().adder_viz_overlay_host(units, n_pops, some.ctypes.data, val.ctypes.data,
+                                       keys.ctypes.data if len(keys) else None, len(keys), run.ctypes.data,
+                                       frames.ctypes.data)
+    if rc != N.OK:
+        raise ValueError("adder_viz_overlay_host refused its arguments")
+    return frames, run
 
 
 class HipVizPlayer(N.Handle):
@@ -135,6 +173,42 @@ class HipVizPlayer(N.Handle):
     def set_buffer_limit(self, buffer_limit):
         rc = self.L.adder_viz_player_set_buffer_limit(self.h, 0 if buffer_limit is None else 1, buffer_limit or 0)
         self._check(rc, 0)
+
+    def detect_features(self, on):
+        """Framer::detect_features; may be switched between any two calls (clears the carried last event)."""
+        self._check(self.L.adder_viz_player_detect_features(self.h, 1 if on else 0), 0)
+
+    def features(self):
+        """The features of the last ingest call: FEATURE_DTYPE records in stream order, index = the global stream index."""
+        count = C.c_uint64(0)
+        self.L.adder_viz_player_features(self.h, None, 0, C.byref(count))
+        out = np.zeros(count.value, N.FRAMER_FEATURE_DTYPE)
+        if count.value:
+            self._check(self.L.adder_viz_player_features(self.h, out.ctypes.data, count.value, C.byref(count)), 0)
+        return out
+
+    def frame_features(self):
+        """One FeatureInterval per frame of the last ingest / finish call: [(end_ts, [n, 2] uint16 {x, y})].
+        .features_error holds the message once a feature could not be filed (the reference would have panicked)."""
+        n = len(self.pop_index)
+        pairs = C.c_uint64(0)
+        end_ts, off = np.zeros(max(n, 1), np.uint64), np.zeros(n + 1, np.uint64)
+        self.L.adder_viz_player_frame_features(self.h, end_ts.ctypes.data, off.ctypes.data, None, 0, C.byref(pairs))
+        xy = np.zeros((max(pairs.value, 1), 2), np.uint16)
+        rc = self.L.adder_viz_player_frame_features(self.h, end_ts.ctypes.data, off.ctypes.data, xy.ctypes.data,
+                                                    pairs.value, C.byref(pairs))
+        self.features_error = None
+        if rc == N.E_BAD_PARAMS:
+            self.features_error = (self.L.adder_viz_player_last_error(self.h) or b"").decode()
+        else:
+            self._check(rc, 0)
+        return [(int(end_ts[j]), xy[int(off[j]): int(off[j + 1])].copy()) for j in range(n)]
+
+    def running_intensities(self):
+        """FrameSequence::get_running_intensities: [height, width, channels] uint8"""
+        out = np.empty(self.shape, np.uint8)
+        self._check(self.L.adder_viz_player_running_intensities(self.h, out.ctypes.data), 0)
+        return out
 
     def running_frame(self):
         out = np.empty(self.shape, np.uint8)
@@ -225,18 +299,23 @@ def parse_header(buf):
 
 
 def viz_play_file(path, buffer_limit=60, playback_speed=1.0, form="running", batch_events=1 << 20, view_mode=0,
-                  max_records=None, device_id=0):
+                  max_records=None, device_id=0, detect_features=False):
     """The adder-viz player on a raw .adder file: yields the frames it shows, one [height, width, channels] uint8 array
     at a time, the flush at the end of the file included.  The file is read in batches of batch_events wire records (a
     batch whose units run past the pending ring is fed in halves);
     max_records cuts the stream short (the cut is then its end).  A bad event ends the run: the frames before it are
-    yielded, then AdderHipError(E_BAD_EVENT) is raised, its .index the event's index in the file."""
+    yielded, then AdderHipError(E_BAD_EVENT) is raised, its .index the event's index in the file.
+    detect_features: the player's feature detection; the "running" frames then carry the crosses, and every item
+    yielded is (frame, (end_ts, [n, 2] uint16 {x, y})): the frame with the FeatureInterval popped with it."""
     with open(path, "rb") as f:
         meta, hb, eb = parse_header(f.read(64))
         f.seek(hb)
         fps = reconstructed_frame_rate(meta["tps"], meta["ref_interval"], meta["source_camera"], playback_speed)
         pl = HipVizPlayer(output_fps=fps, buffer_limit=buffer_limit, view_mode=view_mode, form=form,
                           device_id=device_id, **meta)
+        if detect_features:
+            pl.detect_features(True)
+        with_intervals = (lambda frames: zip(frames, pl.frame_features())) if detect_features else (lambda frames: frames)
         try:
             n_in = 0
             while True:
@@ -257,7 +336,7 @@ def viz_play_file(path, buffer_limit=60, playback_speed=1.0, form="running", bat
                             raise
                         take = (take + 1) // 2
                         continue
-                    for fr in frames:
+                    for fr in with_intervals(frames):
                         yield fr
                     if pl.bad_index is not None:
                         err = N.AdderHipError(E_BAD_EVENT,
@@ -269,7 +348,7 @@ def viz_play_file(path, buffer_limit=60, playback_speed=1.0, form="running", bat
                     at += take
                 if ended:
                     break
-            for fr in pl.finish():
+            for fr in with_intervals(pl.finish()):
                 yield fr
         finally:
             pl.close()

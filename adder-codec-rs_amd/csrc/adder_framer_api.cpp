@@ -11,6 +11,7 @@
 
 #include "../../include/adder_framer.h"
 #include "adder_api_util.hpp"
+#include "adder_feature_intervals.hpp"
 #include "adder_framer_features.h"
 #include "adder_framer_kernels.h"
 
@@ -52,10 +53,6 @@ struct AdderFramer {
     bool poisoned = false;
     std::string err;
     // feature detection while framing (adder_framer_detect_features); allocated when it is first switched on
-    struct FeatureInterval {  // driver.rs:252-257
-        uint64_t end_ts;
-        std::vector<uint16_t> xy;
-    };
     bool detect = false;
     uint8_t *plane = nullptr;            // running_intensities [h][w][c]
     uint32_t *carry = nullptr;           // device {valid, t} of the last event ingested with detection on
@@ -69,9 +66,7 @@ struct AdderFramer {
     int64_t feat_fw = 0;                 // frames_written during that call
     uint64_t feat_index_bias = 0;        // adder_framer_ingest: its device copy starts at the first segment
     std::vector<AdderFramerFeature> feat_host;
-    std::deque<FeatureInterval> intervals;   // FrameSequence::features
-    bool intervals_broken = false;       // the reference would have panicked
-    std::string intervals_err;
+    FeatureIntervals intervals;              // FrameSequence::features
 };
 
 static int ffail(AdderFramer *fr, int code, const char *fmt, ...) {
@@ -554,40 +549,6 @@ extern "C" int adder_framer_flush(AdderFramer *fr, int *frame0_ready) {
 // Feature detection while framing (include/adder_framer.h; kernels in adder_framer_features.hip)
 // ---------------------------------------------------------------------------------------------------------------
 
-// driver.rs:497-549 for one feature found at `time`, with the frames_written the context had during the call
-static void file_feature(AdderFramer *fr, uint32_t time, uint16_t x, uint16_t y, int64_t frames_written) {
-    if (fr->intervals_broken) return;
-    auto &dq = fr->intervals;
-    const uint32_t tpf = fr->tpf;
-    size_t idx = (int64_t)(time / tpf) >= frames_written ? (size_t)(uint32_t)(time / tpf - (uint32_t)frames_written) : 0u;
-    if (time % tpf == 0u && idx > 0u) idx -= 1u;
-    auto broken = [&](const char *why) {
-        char buf[256];
-        snprintf(buf, sizeof buf, "the feature at t = %u (%u, %u) %s (frames_written %lld, %zu intervals): it and every "
-                 "later feature is not filed", time, x, y, why, (long long)frames_written, dq.size());
-        fr->intervals_broken = true;
-        fr->intervals_err = buf;
-    };
-    if (idx >= dq.size()) {
-        if (dq.empty()) {
-            dq.push_back({(uint64_t)tpf, {}});
-            dq.push_back({(uint64_t)tpf * 2u, {}});
-        }
-        const uint64_t new_end_ts = time % tpf == 0u ? time : (uint32_t)((time / tpf + 1u) * tpf);  // u32, wrapping
-        uint64_t running_end_ts = dq.back().end_ts + tpf;
-        if (running_end_ts <= new_end_ts && (new_end_ts - running_end_ts) / tpf >= (1u << 22))
-            return broken("would grow the interval deque by more than 2^22 intervals");
-        while (running_end_ts <= new_end_ts) {
-            dq.push_back({running_end_ts, {}});
-            running_end_ts += tpf;
-        }
-    }
-    if (idx >= dq.size()) return broken("lies past the interval deque, where the reference panics");
-    if (dq[idx].end_ts < (uint64_t)time) dq[idx].end_ts = time;  // detection switched on late (:544-547)
-    dq[idx].xy.push_back(x);
-    dq[idx].xy.push_back(y);
-}
-
 // reads the last call's features back and files them; waits for that call
 static int settle_features(AdderFramer *fr) {
     if (!fr->feat_pending) return ADDER_OK;
@@ -605,7 +566,7 @@ static int settle_features(AdderFramer *fr) {
         FHIPCHK(fr, hipStreamSynchronize(fr->stream));
     }
     fr->feat_pending = false;
-    for (const AdderFramerFeature &f : fr->feat_host) file_feature(fr, f.t, f.x, f.y, fr->feat_fw);
+    for (const AdderFramerFeature &f : fr->feat_host) fr->intervals.file(fr->tpf, f.t, f.x, f.y, fr->feat_fw);
     return ADDER_OK;
 }
 
@@ -752,22 +713,14 @@ extern "C" int adder_framer_pop_features(AdderFramer *fr, uint64_t *end_ts, uint
     FHIPCHK(fr, hipSetDevice(fr->device));
     const int rc = settle_features(fr);
     if (rc != ADDER_OK) return rc;
-    if (fr->intervals_broken) return ffail(fr, ADDER_E_BAD_PARAMS, "%s", fr->intervals_err.c_str());
-    auto &dq = fr->intervals;
-    const size_t n = dq.empty() ? 0u : dq.front().xy.size() / 2u;
+    if (fr->intervals.broken) return ffail(fr, ADDER_E_BAD_PARAMS, "%s", fr->intervals.err.c_str());
+    const size_t n = fr->intervals.front_pairs();
     *count = (uint32_t)n;
     if (n > capacity || (n && !xy))
         return ffail(fr, ADDER_E_OUT_CAPACITY, "%zu features in the interval, room for %u", n, capacity);
-    // driver.rs:851-873
-    if (dq.empty()) {
-        dq.push_back({(uint64_t)fr->tpf, {}});
-        dq.push_back({(uint64_t)fr->tpf * 2u, {}});
-    } else {
-        dq.push_back({(uint64_t)fr->tpf + dq.back().end_ts, {}});
-    }
-    *end_ts = dq.front().end_ts;
-    if (n) memcpy(xy, dq.front().xy.data(), n * 2u * sizeof(uint16_t));
-    dq.pop_front();
+    const FeatureInterval f = fr->intervals.pop(fr->tpf);
+    *end_ts = f.end_ts;
+    if (n) memcpy(xy, f.xy.data(), n * 2u * sizeof(uint16_t));
     return ADDER_OK;
 }
 

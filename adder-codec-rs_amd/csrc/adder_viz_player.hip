@@ -14,11 +14,18 @@
 //      write adjacent bytes of each frame); Some = carried in the pending ring, or covered by an event with index <= P_j;
 //   6. commit: pending values and their Some mask for the frames not popped, counts, trackers, unit state.
 // The host waits once between 4 and 5 (the pop count sizes the output and decides whether anything is committed).
+// A call made with feature detection on (adder_viz_player_features.hpp) adds: an arm of the walk that leaves each
+// event's u8 value and t_after by input index; the FAST candidates, a thread per event, before the schedule; behind it
+// the period-start mask, a scan and the feature records with the frames_written of their period; a cursor through the
+// call's cross stamps in the hand-out (whenever the popped intervals hold features); the plane in the commit.  The host
+// then waits once more, to read the features back before the crosses go up.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 #include "../../include/adder_viz_player.h"
+#include "adder_framer_features.hpp"
+#include "adder_viz_player_features.hpp"
 #include "adder_viz_player_kernels.h"
 #include "adder_viz_player_logic.hpp"
 #include "adder_wire.hpp"
@@ -33,6 +40,7 @@ __global__ void viz_init_kernel(VizScalars *sc, uint64_t n) {
     sc->overflow = 0u;
     sc->w_end = 0;
     sc->m_end = -1;
+    sc->n_feat = 0u;
 }
 
 template <int SRC>
@@ -59,13 +67,16 @@ __global__ __launch_bounds__(256) void viz_keys_kernel(const void *__restrict__ 
     l_in[i] = -1;
 }
 
-// A thread per run: the unit's chain, event by event (framer_step), from the carried FramerPx.
-template <int SRC>
+// A thread per run: the unit's chain, event by event (framer_step), from the carried FramerPx.  DET: the arm of a call
+// made with detection on also leaves, by input index, the unit's u8 value after the event and the t that
+// ingest_event_for_chunk left in it (framer_feature_step).
+template <int SRC, bool DET>
 __global__ __launch_bounds__(256) void viz_walk_kernel(const void *__restrict__ in, uint64_t n, VizArgs a, int32_t w0,
                                                        const uint32_t *__restrict__ ukeys,
                                                        const uint32_t *__restrict__ uidx, int32_t *__restrict__ s_l,
                                                        uint8_t *__restrict__ s_val, FramerPx *__restrict__ s_px,
-                                                       int32_t *__restrict__ l_in, VizScalars *sc) {
+                                                       int32_t *__restrict__ l_in, uint8_t *__restrict__ val_in,
+                                                       uint32_t *__restrict__ t_after, VizScalars *sc) {
     const uint64_t j0 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (j0 >= n) return;
     const uint32_t u = ukeys[j0];
@@ -80,7 +91,18 @@ __global__ __launch_bounds__(256) void viz_walk_kernel(const void *__restrict__ 
         const WireEv e = wire_load<SRC>(in, i);
         const bool checked = !(a.k.abs_t && p.ts >= (uint64_t)e.t);
         int32_t from = 0, to = 0;
-        if (framer_step(p, e.d, e.t, a.k, from, to, overflow) && (int64_t)to >= past_ring) deep = true;
+        bool fills;
+        if (DET) {
+            const FramerFeatureStep o = framer_feature_step(p, e.d, e.t, a.k);
+            fills = o.fills;
+            to = o.to;
+            overflow = overflow || o.overflow;
+            val_in[i] = (uint8_t)o.val8;
+            t_after[i] = o.t_after;
+        } else {
+            fills = framer_step(p, e.d, e.t, a.k, from, to, overflow);
+        }
+        if (fills && (int64_t)to >= past_ring) deep = true;
         s_l[j] = p.lastf;
         s_val[j] = (uint8_t)p.lasti;
         if (checked) l_in[i] = p.lastf;
@@ -197,15 +219,21 @@ __global__ __launch_bounds__(256) void viz_schedule_kernel(VizSchedIn v, int32_t
 // 64 consecutive bytes.  Reads per unit: 8 B of run bounds, 16 B of carried state, per frame one byte of the carried
 // Some mask (plus the value when set), and its run once overall (the cursor only moves forward: 4 B of L and 4 B of
 // index per event, one byte of value per covering event).
+// STAMPS: a second cursor runs through the unit's cross stamps (sorted by unit, then frame); the running value after
+// frame k is the later of the last Some and the last stamp at or before k, and the stamp wins inside a frame.
+template <bool STAMPS>
 __global__ __launch_bounds__(256) void viz_handout_kernel(VizArgs a, uint64_t lim, int32_t w0, uint32_t n_pops, int form,
                                                           const uint32_t *__restrict__ uidx,
                                                           const int32_t *__restrict__ s_l,
                                                           const uint8_t *__restrict__ s_val,
                                                           const FramerPx *__restrict__ s_px,
                                                           const int32_t *__restrict__ pops,
-                                                          const uint8_t *__restrict__ flushed, uint8_t *__restrict__ out) {
+                                                          const uint8_t *__restrict__ flushed,
+                                                          const unsigned long long *__restrict__ stamps,
+                                                          uint32_t n_stamps, uint8_t *__restrict__ out) {
     const uint32_t u = blockIdx.x * 256u + threadIdx.x;
     if (u >= a.units) return;
+    uint32_t q = STAMPS ? viz_stamp_first(stamps, n_stamps, u) : 0u;
     const uint32_t first = a.run_lo[u], end = a.run_lo[u + 1u];
     const FramerPx old = a.px[u];
     const bool stepped = first < end && (uint64_t)uidx[first] < lim;
@@ -231,7 +259,7 @@ __global__ __launch_bounds__(256) void viz_handout_kernel(VizArgs a, uint64_t li
             some = true;
             v = lasti;
         }
-        if (some) cur = v;
+        cur = viz_running_step(cur, some, v, STAMPS && viz_stamp_take(stamps, n_stamps, q, u, k));
         out[(size_t)k * a.units + u] = (uint8_t)(form == ADDER_VIZ_FRAME_RUNNING ? cur : (some ? v : 0u));
     }
     a.running[u] = (uint8_t)cur;
@@ -282,21 +310,94 @@ __global__ __launch_bounds__(256) void viz_commit_rows_kernel(VizArgs a, int32_t
     if (slot == 0u) a.done[r] = done_new[r];
 }
 
+// ---- feature detection (launched only by calls made with detection on) ----------------------------------------------
+
+// A thread per event in input order: driver.rs:491-494 on the plane as it stood right before the event.  A ring pixel's
+// value is the one its unit's last earlier event of this call left (a search in the unit's run), or the carried plane.
+// Does not depend on the schedule.
+template <int SRC>
+__global__ __launch_bounds__(256) void viz_candidates_kernel(const void *__restrict__ in, uint64_t n, VizArgs a,
+                                                             const uint32_t *__restrict__ uidx,
+                                                             const uint8_t *__restrict__ s_val, VizDetect d,
+                                                             const VizScalars *sc) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    bool feature = false;
+    if (i < wire_limit(sc->bad, sc->eof)) {
+        const WireEv e = wire_load<SRC>(in, i);
+        const bool last_valid = i > 0u ? true : d.carry_valid != 0u;
+        const uint32_t last_t = i > 0u ? d.t_after[i - 1u] : d.carry_t;
+        if (framer_feature_is_candidate(e.x, e.y, e.c, e.t, last_valid, last_t, a.width, a.height)) {
+            feature = fast9_ring_is_feature((int)d.val_in[i], [&](uint32_t k) -> int {
+                const uint32_t rx = (uint32_t)((int)e.x + fast_ring_dx(k)), ry = (uint32_t)((int)e.y + fast_ring_dy(k));
+                const uint32_t ru = (ry * a.width + rx) * a.channels;  // channel 0 of the ring pixel (cv.rs:77-87)
+                return (int)framer_feature_value_before(uidx, s_val, a.run_lo[ru], a.run_lo[ru + 1u], (uint32_t)i,
+                                                        d.plane[ru]);
+            });
+        }
+    }
+    d.mark[i] = feature ? 1u : 0u;
+}
+
+// behind the schedule: the first event of a period is never tested
+__global__ __launch_bounds__(256) void viz_feat_flag_kernel(uint64_t n, VizDetect d, const int32_t *__restrict__ pops,
+                                                            const VizScalars *sc) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    d.flag[i] = (d.mark[i] != 0u && !viz_period_start(pops, sc->n_pops, (int64_t)i)) ? 1u : 0u;
+}
+
+template <int SRC>
+__global__ __launch_bounds__(256) void viz_feat_store_kernel(const void *__restrict__ in, uint64_t n, int32_t w0,
+                                                             VizDetect d, const int32_t *__restrict__ pops,
+                                                             VizScalars *sc) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t f = d.flag[i], o = d.offs[i];
+    if (i == n - 1u) sc->n_feat = o + f;
+    if (f == 0u) return;
+    const WireEv e = wire_load<SRC>(in, i);
+    AdderFramerFeature r;
+    r.index = d.index_base + i;
+    r.t = e.t;  // the raw t, also in a DeltaT stream (driver.rs:446)
+    r.x = (uint16_t)e.x;
+    r.y = (uint16_t)e.y;
+    d.feat[o] = r;
+    d.feat_w[o] = w0 + (int32_t)viz_pops_before(pops, sc->n_pops, (int64_t)i);
+}
+
+// the last event of every run that counts writes the plane
+__global__ __launch_bounds__(256) void viz_commit_plane_kernel(uint64_t n, uint64_t lim, VizArgs a,
+                                                               const uint32_t *__restrict__ ukeys,
+                                                               const uint32_t *__restrict__ uidx,
+                                                               const FramerPx *__restrict__ s_px,
+                                                               uint8_t *__restrict__ plane) {
+    const uint64_t j0 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (j0 >= n) return;
+    const uint32_t u = ukeys[j0];
+    if (u >= a.units || (j0 > 0u && ukeys[j0 - 1] == u) || (uint64_t)uidx[j0] >= lim) return;
+    const uint32_t v = s_px[j0].lasti;
+    plane[u] = (uint8_t)(v > 255u ? 255u : v);
+}
+
 size_t viz_temp_bytes(uint64_t n) {
-    size_t a = 0, b = 0, c = 0;
+    size_t a = 0, b = 0, c = 0, d = 0;
     hipcub::DoubleBuffer<uint32_t> k(nullptr, nullptr), v(nullptr, nullptr);
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, k, v, (int)n);
     (void)hipcub::DeviceScan::InclusiveScan(nullptr, b, (const int32_t *)nullptr, (int32_t *)nullptr, hipcub::Max(), (int)n);
     (void)hipcub::DeviceScan::InclusiveScan(nullptr, c, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
                                             hipcub::Max(), (int)n);
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, d, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n);
     if (b > a) a = b;
     if (c > a) a = c;
+    if (d > a) a = d;
     return a + 256;
 }
 
 template <int SRC>
 static hipError_t viz_prepare_src(const VizArgs &a, const void *in, uint64_t n, int32_t w0, int32_t m0, int has_limit,
-                                  uint32_t limit, int opening, int finish, VizScratch &s, hipStream_t stream) {
+                                  uint32_t limit, int opening, int finish, VizScratch &s, const VizDetect &det,
+                                  hipStream_t stream) {
     const uint32_t grid = (uint32_t)((n + 255u) / 256u);
     const size_t cells = (size_t)a.height * a.ring;
     hipError_t e = hipMemsetAsync(s.cnt_call, 0, cells * 4u, stream);
@@ -323,8 +424,12 @@ static hipError_t viz_prepare_src(const VizArgs &a, const void *in, uint64_t n, 
         if (e != hipSuccess) return e;
         s.rkeys = rk.Current();
         s.ridx = rv.Current();
-        hipLaunchKernelGGL((viz_walk_kernel<SRC>), dim3(grid), dim3(256), 0, stream, in, n, a, w0, s.ukeys, s.uidx, s.s_l,
-                           s.s_val, s.s_px, s.l_in, s.sc);
+        if (det.plane)
+            hipLaunchKernelGGL((viz_walk_kernel<SRC, true>), dim3(grid), dim3(256), 0, stream, in, n, a, w0, s.ukeys,
+                               s.uidx, s.s_l, s.s_val, s.s_px, s.l_in, det.val_in, det.t_after, s.sc);
+        else
+            hipLaunchKernelGGL((viz_walk_kernel<SRC, false>), dim3(grid), dim3(256), 0, stream, in, n, a, w0, s.ukeys,
+                               s.uidx, s.s_l, s.s_val, s.s_px, s.l_in, (uint8_t *)nullptr, (uint32_t *)nullptr, s.sc);
         hipLaunchKernelGGL(viz_coverage_kernel, dim3(grid), dim3(256), 0, stream, n, a, w0, s.ukeys, s.uidx, s.s_l,
                            s.cnt_call, s.nat_call, s.sc);
         hipLaunchKernelGGL(viz_comb_kernel, dim3(grid), dim3(256), 0, stream, n, s.rkeys, s.ridx, s.l_in, s.comb_in);
@@ -338,6 +443,9 @@ static hipError_t viz_prepare_src(const VizArgs &a, const void *in, uint64_t n, 
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(viz_bounds_kernel, dim3((a.units + 1u + 255u) / 256u), dim3(256), 0, stream, n, a, s.ukeys);
+    if (det.plane && n > 0u)
+        hipLaunchKernelGGL((viz_candidates_kernel<SRC>), dim3(grid), dim3(256), 0, stream, in, n, a, s.uidx, s.s_val, det,
+                           s.sc);
     VizSchedIn v{};
     v.n = 0;  // the kernel takes it from the scalars
     v.n_all = (int64_t)n;
@@ -359,23 +467,39 @@ static hipError_t viz_prepare_src(const VizArgs &a, const void *in, uint64_t n, 
     v.finish = finish;
     v.max_pops = a.ring + 1u;
     hipLaunchKernelGGL(viz_schedule_kernel, dim3(1), dim3(256), 0, stream, v, s.pops, s.flushed, s.done_new, s.sc);
+    if (det.plane && n > 0u) {
+        hipLaunchKernelGGL(viz_feat_flag_kernel, dim3(grid), dim3(256), 0, stream, n, det, s.pops, s.sc);
+        size_t temp_bytes = s.temp_bytes;
+        const hipError_t e2 = hipcub::DeviceScan::ExclusiveSum(s.temp, temp_bytes, (const uint32_t *)det.flag, det.offs,
+                                                               (int)n, stream);
+        if (e2 != hipSuccess) return e2;
+        hipLaunchKernelGGL((viz_feat_store_kernel<SRC>), dim3(grid), dim3(256), 0, stream, in, n, w0, det, s.pops, s.sc);
+    }
     return hipGetLastError();
 }
 
 hipError_t viz_prepare(const VizArgs &a, int source, const void *in, uint64_t n, int32_t w0, int32_t m0, int has_limit,
-                       uint32_t limit, int opening, int finish, VizScratch &s, hipStream_t stream) {
-    if (source == kSrcEvents) return viz_prepare_src<kSrcEvents>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, stream);
-    if (source == kSrcWire9) return viz_prepare_src<kSrcWire9>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, stream);
-    return viz_prepare_src<kSrcWire11>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, stream);
+                       uint32_t limit, int opening, int finish, VizScratch &s, const VizDetect &det, hipStream_t stream) {
+    if (source == kSrcEvents)
+        return viz_prepare_src<kSrcEvents>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, det, stream);
+    if (source == kSrcWire9)
+        return viz_prepare_src<kSrcWire9>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, det, stream);
+    return viz_prepare_src<kSrcWire11>(a, in, n, w0, m0, has_limit, limit, opening, finish, s, det, stream);
 }
 
 hipError_t viz_handout_commit(const VizArgs &a, uint64_t n, uint64_t lim, int32_t w0, uint32_t n_pops, int form,
-                              uint8_t *d_frames, const VizScratch &s, hipStream_t stream) {
+                              uint8_t *d_frames, const VizScratch &s, const unsigned long long *stamps,
+                              uint32_t n_stamps, const VizDetect &det, hipStream_t stream) {
     const uint32_t grid = (uint32_t)((n + 255u) / 256u);
     const int32_t w_end = w0 + (int32_t)n_pops;
     if (n_pops > 0u) {
-        hipLaunchKernelGGL(viz_handout_kernel, dim3((a.units + 255u) / 256u), dim3(256), 0, stream, a, lim, w0, n_pops,
-                           form, s.uidx, s.s_l, s.s_val, s.s_px, s.pops, s.flushed, d_frames);
+        if (n_stamps > 0u)
+            hipLaunchKernelGGL(viz_handout_kernel<true>, dim3((a.units + 255u) / 256u), dim3(256), 0, stream, a, lim, w0,
+                               n_pops, form, s.uidx, s.s_l, s.s_val, s.s_px, s.pops, s.flushed, stamps, n_stamps, d_frames);
+        else
+            hipLaunchKernelGGL(viz_handout_kernel<false>, dim3((a.units + 255u) / 256u), dim3(256), 0, stream, a, lim, w0,
+                               n_pops, form, s.uidx, s.s_l, s.s_val, s.s_px, s.pops, s.flushed,
+                               (const unsigned long long *)nullptr, 0u, d_frames);
         // the popped frames' slots serve frames w0 + ring .. from here on: no Some left in them (n_pops <= ring)
         const uint32_t s0 = (uint32_t)(w0 % (int32_t)a.ring);
         const uint32_t head = n_pops < a.ring - s0 ? n_pops : a.ring - s0;
@@ -390,6 +514,9 @@ hipError_t viz_handout_commit(const VizArgs &a, uint64_t n, uint64_t lim, int32_
         hipLaunchKernelGGL(viz_commit_ring_kernel, dim3(grid), dim3(256), 0, stream, n, lim, a, w_end, s.ukeys, s.uidx,
                            s.s_l, s.s_val);
         hipLaunchKernelGGL(viz_commit_px_kernel, dim3(grid), dim3(256), 0, stream, n, lim, a, s.ukeys, s.uidx, s.s_px);
+        if (det.plane)
+            hipLaunchKernelGGL(viz_commit_plane_kernel, dim3(grid), dim3(256), 0, stream, n, lim, a, s.ukeys, s.uidx,
+                               s.s_px, det.plane);
     }
     hipLaunchKernelGGL(viz_commit_rows_kernel, dim3((a.height * a.ring + 255u) / 256u), dim3(256), 0, stream, a, w0, w_end,
                        s.cnt_call, s.done_new);

@@ -11,6 +11,8 @@
 
 #include "../../include/adder_viz_player.h"
 #include "adder_api_util.hpp"
+#include "adder_feature_intervals.hpp"
+#include "adder_viz_player_features.hpp"
 #include "adder_viz_player_kernels.h"
 #include "adder_viz_player_logic.hpp"
 #include "adder_wire.hpp"
@@ -40,6 +42,22 @@ struct AdderVizPlayer {
     void *d_out = nullptr;
     size_t d_out_cap = 0;
     std::string err;
+    // feature detection (adder_viz_player_detect_features); the device side is allocated when it is first switched on
+    bool detect = false;
+    uint8_t *plane = nullptr;      // running_intensities
+    bool carry_valid = false;      // the carried last event {valid, t}: host scalars, like the schedule's
+    uint32_t carry_t = 0;
+    uint32_t *h_tail = nullptr;    // pinned: t_after of the call's last event
+    void *det_block = nullptr;     // the per-call arrays of VizDetect, carved from one allocation that only grows
+    size_t det_block_cap = 0;
+    FeatureIntervals intervals;    // FrameSequence::features: runs from creation, one pop per popped frame
+    std::vector<AdderFramerFeature> feat_host;  // the last ingest call's features
+    std::vector<int32_t> feat_w_host;
+    std::vector<uint64_t> fi_end, fi_off;       // the intervals popped by the last ingest / finish call
+    std::vector<uint16_t> fi_xy;
+    std::vector<unsigned long long> stamps;     // its cross stamps
+    void *d_stamps = nullptr;
+    size_t d_stamps_cap = 0;
 };
 
 static int vfail(AdderVizPlayer *v, int code, const char *fmt, ...) {
@@ -74,8 +92,10 @@ static void viz_free(AdderVizPlayer *v) {
     (void)hipDeviceSynchronize();
     free_scratch(v);
     api_free_all({v->a.px, v->a.ring_val, v->a.ring_some, v->a.running, v->a.cnt, v->a.done, v->a.run_lo, v->s.cnt_call,
-                  v->s.nat_call, v->s.done_new, v->s.pops, v->s.flushed, v->s.sc, v->d_in, v->d_out});
+                  v->s.nat_call, v->s.done_new, v->s.pops, v->s.flushed, v->s.sc, v->d_in, v->d_out, v->plane, v->det_block,
+                  v->d_stamps});
     if (v->h_sc) (void)hipHostFree(v->h_sc);
+    if (v->h_tail) (void)hipHostFree(v->h_tail);
     if (v->h_pops) (void)hipHostFree(v->h_pops);
     if (v->stream) (void)hipStreamDestroy(v->stream);
     delete v;
@@ -120,7 +140,15 @@ static int reset_state(AdderVizPlayer *v) {
     VHIPCHK(v, hipMemset(a.running, 0, u));
     VHIPCHK(v, hipMemset(a.cnt, 0, cells * 4u));
     VHIPCHK(v, hipMemset(a.done, 0, a.height));
+    if (v->plane) VHIPCHK(v, hipMemset(v->plane, 0, u));
     VHIPCHK(v, hipDeviceSynchronize());  // the calls run on other streams
+    v->carry_valid = false;
+    v->intervals.clear();
+    v->feat_host.clear();
+    v->feat_w_host.clear();
+    v->fi_end.clear();
+    v->fi_off.assign(1, 0u);
+    v->fi_xy.clear();
     v->frames_written = 0;
     v->m = -1;
     v->n_events = 0;
@@ -225,7 +253,82 @@ extern "C" int adder_viz_player_set_buffer_limit(AdderVizPlayer *v, int has, uin
     v->has_limit = has ? 1 : 0;
     v->limit = limit;
     v->limit_set = true;
+    v->carry_valid = false;  // adaptive_state_update lies between two `consume` calls: last_event = None (adder.rs:409)
     return ADDER_OK;
+}
+
+extern "C" int adder_viz_player_detect_features(AdderVizPlayer *v, int on) {
+    if (!v) return ADDER_E_BAD_PARAMS;
+    if (on && !v->plane) {
+        VHIPCHK(v, hipSetDevice(v->p.device_id));
+        VHIPCHK(v, hipMalloc((void **)&v->plane, v->a.units));
+        VHIPCHK(v, hipMemset(v->plane, 0, v->a.units));
+        VHIPCHK(v, hipHostMalloc((void **)&v->h_tail, sizeof(uint32_t), hipHostMallocDefault));
+        VHIPCHK(v, hipDeviceSynchronize());
+    }
+    v->detect = on != 0;
+    v->carry_valid = false;  // a UI update lies between two `consume` calls
+    return ADDER_OK;
+}
+
+static size_t det_align(size_t b) { return (b + 255u) & ~(size_t)255u; }
+
+// the per-call arrays of a call of n events made with detection on
+static int det_scratch(AdderVizPlayer *v, uint64_t n, VizDetect *d) {
+    const size_t c = (size_t)n + 1u;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = off;
+        off += det_align(bytes);
+        return at;
+    };
+    const size_t o_val = carve(c), o_ta = carve(4u * c), o_mk = carve(c), o_fl = carve(4u * c), o_of = carve(4u * c),
+                 o_ft = carve(sizeof(AdderFramerFeature) * c), o_fw = carve(4u * c);
+    VHIPCHK(v, api_grow(&v->det_block, &v->det_block_cap, off));
+    uint8_t *b = (uint8_t *)v->det_block;
+    d->val_in = b + o_val;
+    d->t_after = (uint32_t *)(b + o_ta);
+    d->mark = b + o_mk;
+    d->flag = (uint32_t *)(b + o_fl);
+    d->offs = (uint32_t *)(b + o_of);
+    d->feat = (AdderFramerFeature *)(b + o_ft);
+    d->feat_w = (int32_t *)(b + o_fw);
+    return ADDER_OK;
+}
+
+// The deque bookkeeping of one call, in event / pop order: a feature of event i is filed before the frames popped
+// after an event >= i (under the frames_written of its period), every popped frame takes one interval.  Leaves the
+// intervals in fi_* and their crosses (adder.rs:359-388: radius 2, both arms, every channel) as sorted stamps.  nf: the
+// features of feat_host to file (none at finish, which keeps the last ingest call's list).
+static void file_and_pop(AdderVizPlayer *v, uint32_t n_pops, size_t nf) {
+    const VizArgs &a = v->a;
+    v->fi_end.clear();
+    v->fi_off.assign(1, 0u);
+    v->fi_xy.clear();
+    v->stamps.clear();
+    size_t f = 0;
+    auto file_until = [&](int64_t last_index) {  // global index
+        for (; f < nf && (int64_t)v->feat_host[f].index <= last_index; ++f)
+            v->intervals.file(v->tpf, v->feat_host[f].t, v->feat_host[f].x, v->feat_host[f].y, v->feat_w_host[f]);
+    };
+    for (uint32_t k = 0; k < n_pops; ++k) {
+        file_until((int64_t)v->n_events + (int64_t)v->h_pops[k]);
+        const FeatureInterval iv = v->intervals.pop(v->tpf);
+        v->fi_end.push_back(iv.end_ts);
+        for (size_t q = 0; q + 1u < iv.xy.size(); q += 2u) {
+            const uint32_t x = iv.xy[q], y = iv.xy[q + 1u];
+            v->fi_xy.push_back((uint16_t)x);
+            v->fi_xy.push_back((uint16_t)y);
+            for (int i = -2; i <= 2; ++i)
+                for (uint32_t c = 0; c < a.channels; ++c) {  // never out of bounds: a feature is 3 pixels off the border
+                    v->stamps.push_back(viz_stamp_key((((uint32_t)((int)y + i)) * a.width + x) * a.channels + c, k));
+                    v->stamps.push_back(viz_stamp_key((y * a.width + (uint32_t)((int)x + i)) * a.channels + c, k));
+                }
+        }
+        v->fi_off.push_back(v->fi_xy.size() / 2u);
+    }
+    file_until(INT64_MAX);
+    std::sort(v->stamps.begin(), v->stamps.end());
 }
 
 // One call: everything up to the schedule, a wait for the pop count, then the hand-out into d_frames (device) or, when
@@ -249,8 +352,17 @@ static int run(AdderVizPlayer *v, int source, const void *d_in, uint64_t n, int 
     int rc = ensure_scratch(v, n);
     if (rc != ADDER_OK) return rc;
     const VizArgs &a = v->a;
+    VizDetect det{};
+    if (v->detect && !finish) {
+        rc = det_scratch(v, n, &det);
+        if (rc != ADDER_OK) return rc;
+        det.plane = v->plane;
+        det.carry_valid = v->carry_valid ? 1u : 0u;
+        det.carry_t = v->carry_t;
+        det.index_base = v->n_events;
+    }
     VHIPCHK(v, viz_prepare(a, source, d_in, n, v->frames_written, v->m, v->has_limit, v->limit,
-                           v->limit_set ? 1 : 0, finish, v->s, stream));
+                           v->limit_set ? 1 : 0, finish, v->s, det, stream));
     VHIPCHK(v, hipMemcpyAsync(v->h_sc, v->s.sc, sizeof(VizScalars), hipMemcpyDeviceToHost, stream));
     VHIPCHK(v, hipMemcpyAsync(v->h_pops, v->s.pops, ((size_t)a.ring + 1u) * 4u, hipMemcpyDeviceToHost, stream));
     VHIPCHK(v, hipStreamSynchronize(stream));
@@ -265,15 +377,42 @@ static int run(AdderVizPlayer *v, int source, const void *d_in, uint64_t n, int 
     if (n_frames) *n_frames = sc.n_pops;
     if (sc.n_pops > frame_cap)
         return vfail(v, ADDER_E_OUT_CAPACITY, "%u frames do not fit in %llu", sc.n_pops, (unsigned long long)frame_cap);
+    // From here on the call is not refused; only a HIP error can still end it, and that leaves the context unusable (the
+    // header says so).  Its features come back (one more wait, with detection on only), the host files them and pops
+    // one interval per frame, and the crosses go up as stamps.
+    if (!finish) {
+        v->feat_host.resize(det.plane ? sc.n_feat : 0u);
+        v->feat_w_host.resize(v->feat_host.size());
+        if (!v->feat_host.empty()) {
+            VHIPCHK(v, hipMemcpyAsync(v->feat_host.data(), det.feat, v->feat_host.size() * sizeof(AdderFramerFeature),
+                                      hipMemcpyDeviceToHost, stream));
+            VHIPCHK(v, hipMemcpyAsync(v->feat_w_host.data(), det.feat_w, v->feat_w_host.size() * 4u, hipMemcpyDeviceToHost,
+                                      stream));
+            VHIPCHK(v, hipStreamSynchronize(stream));
+        }
+    }
+    file_and_pop(v, sc.n_pops, finish ? 0u : v->feat_host.size());
+    const uint32_t n_stamps = (uint32_t)v->stamps.size();
+    if (n_stamps) {
+        VHIPCHK(v, api_grow(&v->d_stamps, &v->d_stamps_cap, (size_t)n_stamps * 8u));
+        VHIPCHK(v, hipMemcpyAsync(v->d_stamps, v->stamps.data(), (size_t)n_stamps * 8u, hipMemcpyHostToDevice, stream));
+    }
     const size_t fb = a.units;
     if (h_frames) {
         VHIPCHK(v, api_grow(&v->d_out, &v->d_out_cap, (size_t)sc.n_pops * fb + 8u));
         d_frames = (uint8_t *)v->d_out;
     }
-    VHIPCHK(v, viz_handout_commit(a, n, lim, v->frames_written, sc.n_pops, form, d_frames, v->s, stream));
+    VHIPCHK(v, viz_handout_commit(a, n, lim, v->frames_written, sc.n_pops, form, d_frames, v->s,
+                                  (const unsigned long long *)v->d_stamps, n_stamps, det, stream));
     if (h_frames && sc.n_pops)
         VHIPCHK(v, hipMemcpyAsync(h_frames, d_frames, (size_t)sc.n_pops * fb, hipMemcpyDeviceToHost, stream));
+    if (det.plane && lim > 0u)
+        VHIPCHK(v, hipMemcpyAsync(v->h_tail, det.t_after + (lim - 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     VHIPCHK(v, hipStreamSynchronize(stream));
+    if (det.plane && lim > 0u) {  // last_event, unless the call's last event ended a period
+        v->carry_valid = !(sc.n_pops > 0u && (uint64_t)((int64_t)v->h_pops[sc.n_pops - 1u] + 1) == lim);
+        v->carry_t = *v->h_tail;
+    }
     if (pop_index)
         for (uint32_t k = 0; k < sc.n_pops; ++k) pop_index[k] = (int64_t)v->n_events + (int64_t)v->h_pops[k];
     v->frames_written = sc.w_end;
@@ -354,6 +493,89 @@ extern "C" int adder_viz_player_running_frame(AdderVizPlayer *v, uint8_t *frame)
     VHIPCHK(v, hipSetDevice(v->p.device_id));
     VHIPCHK(v, hipMemcpyAsync(frame, v->a.running, v->a.units, hipMemcpyDeviceToHost, v->stream));
     VHIPCHK(v, hipStreamSynchronize(v->stream));
+    return ADDER_OK;
+}
+
+extern "C" int adder_viz_player_features(AdderVizPlayer *v, AdderFramerFeature *out, uint64_t capacity, uint64_t *count) {
+    if (!v || !count) return ADDER_E_BAD_PARAMS;
+    *count = v->feat_host.size();
+    if (*count > capacity || (*count && !out))
+        return vfail(v, ADDER_E_OUT_CAPACITY, "%llu features, room for %llu", (unsigned long long)*count,
+                     (unsigned long long)capacity);
+    if (*count) memcpy(out, v->feat_host.data(), (size_t)*count * sizeof(AdderFramerFeature));
+    return ADDER_OK;
+}
+
+extern "C" int adder_viz_player_frame_features(AdderVizPlayer *v, uint64_t *end_ts, uint64_t *offsets, uint16_t *xy,
+                                               uint64_t xy_capacity, uint64_t *n_pairs) {
+    if (!v || !n_pairs) return ADDER_E_BAD_PARAMS;
+    const size_t frames = v->fi_end.size();
+    if (!offsets || (frames && !end_ts)) return vfail(v, ADDER_E_BAD_PARAMS, "null offsets / end_ts");
+    *n_pairs = v->fi_xy.size() / 2u;
+    if (*n_pairs > xy_capacity || (*n_pairs && !xy))
+        return vfail(v, ADDER_E_OUT_CAPACITY, "%llu features in the frames' intervals, room for %llu",
+                     (unsigned long long)*n_pairs, (unsigned long long)xy_capacity);
+    if (frames) memcpy(end_ts, v->fi_end.data(), frames * sizeof(uint64_t));
+    memcpy(offsets, v->fi_off.data(), (frames + 1u) * sizeof(uint64_t));
+    if (*n_pairs) memcpy(xy, v->fi_xy.data(), v->fi_xy.size() * sizeof(uint16_t));
+    if (v->intervals.broken) return vfail(v, ADDER_E_BAD_PARAMS, "%s", v->intervals.err.c_str());
+    return ADDER_OK;
+}
+
+extern "C" int adder_viz_player_running_intensities(AdderVizPlayer *v, uint8_t *out) {
+    if (!v || !out) return ADDER_E_BAD_PARAMS;
+    if (!v->plane) {  // detection was never on
+        memset(out, 0, v->a.units);
+        return ADDER_OK;
+    }
+    VHIPCHK(v, hipSetDevice(v->p.device_id));
+    VHIPCHK(v, hipMemcpyAsync(out, v->plane, v->a.units, hipMemcpyDeviceToHost, v->stream));
+    VHIPCHK(v, hipStreamSynchronize(v->stream));
+    return ADDER_OK;
+}
+
+extern "C" int adder_viz_player_running_intensities_device(AdderVizPlayer *v, uint8_t *d_out, void *stream) {
+    if (!v || !d_out) return ADDER_E_BAD_PARAMS;
+    VHIPCHK(v, hipSetDevice(v->p.device_id));
+    if (!v->plane) {
+        VHIPCHK(v, hipMemsetAsync(d_out, 0, v->a.units, (hipStream_t)stream));
+        return ADDER_OK;
+    }
+    VHIPCHK(v, hipMemcpyAsync(d_out, v->plane, v->a.units, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return ADDER_OK;
+}
+
+// The three places where the pop schedule meets detection, on the host (self-tests): the functions the kernels run.
+// mark_out[i] = mark[i] unless event i is the first of a period; w_out[i] = w0 + the pops before event i.
+extern "C" int adder_viz_features_host(const int32_t *pops, uint32_t n_pops, uint64_t n, const uint8_t *mark, int32_t w0,
+                                       uint8_t *mark_out, int32_t *w_out) {
+    if ((n_pops && !pops) || (n && (!mark || !mark_out || !w_out))) return ADDER_E_BAD_PARAMS;
+    for (uint32_t k = 1; k < n_pops; ++k)
+        if (pops[k] < pops[k - 1]) return ADDER_E_BAD_PARAMS;
+    for (uint64_t i = 0; i < n; ++i) {
+        mark_out[i] = (mark[i] != 0u && !viz_period_start(pops, n_pops, (int64_t)i)) ? 1u : 0u;
+        w_out[i] = w0 + (int32_t)viz_pops_before(pops, n_pops, (int64_t)i);
+    }
+    return ADDER_OK;
+}
+
+// The hand-out's running frame: some / val are [n_pops][units] (the popped frames), stamps the sorted viz_stamp_key
+// list; running is read and left as the context's running frame would be, frames receives the RUNNING form.
+extern "C" int adder_viz_overlay_host(uint32_t units, uint32_t n_pops, const uint8_t *some, const uint8_t *val,
+                                      const uint64_t *stamps, uint32_t n_stamps, uint8_t *running, uint8_t *frames) {
+    if (!running || (n_pops && (!some || !val || !frames)) || (n_stamps && !stamps)) return ADDER_E_BAD_PARAMS;
+    for (uint32_t q = 1; q < n_stamps; ++q)
+        if (stamps[q] < stamps[q - 1]) return ADDER_E_BAD_PARAMS;
+    const unsigned long long *st = reinterpret_cast<const unsigned long long *>(stamps);
+    for (uint32_t u = 0; u < units; ++u) {
+        uint32_t q = viz_stamp_first(st, n_stamps, u), cur = running[u];
+        for (uint32_t k = 0; k < n_pops; ++k) {
+            const size_t at = (size_t)k * units + u;
+            cur = viz_running_step(cur, some[at] != 0u, val[at], viz_stamp_take(st, n_stamps, q, u, k));
+            frames[at] = (uint8_t)cur;
+        }
+        running[u] = (uint8_t)cur;
+    }
     return ADDER_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/adder_framer.h"  // AdderFramerFeature
 #include "adder_framer.hpp"
 
 namespace adder {
@@ -16,6 +17,7 @@ struct VizScalars {  // device words of one call, read back once the schedule is
     uint32_t status;         // kVizStatus*
     uint32_t n_pops, overflow;
     int32_t w_end, m_end;
+    uint32_t n_feat;  // features of the call (detection on)
 };
 
 struct VizArgs {
@@ -53,13 +55,32 @@ struct VizScratch {  // per call; n entries unless said otherwise
     const uint32_t *ukeys, *uidx, *rkeys, *ridx;  // the sorted arrays, set by viz_prepare
 };
 
+// Feature detection (adder_viz_player_features.hpp): what a call made with detection on adds.  Null plane: off.
+struct VizDetect {
+    uint8_t *plane;               // carried running_intensities [height][width][channels]
+    uint32_t carry_valid, carry_t;  // the carried last event
+    uint64_t index_base;          // global index of the call's first event
+    // per call, n entries, input order
+    uint8_t *val_in;              // the unit's u8 value after the event
+    uint32_t *t_after;            // the t ingest_event_for_chunk left in the event
+    uint8_t *mark;                // FAST candidates that are corners
+    uint32_t *flag, *offs;        // ... that are not the first event of a period, and their exclusive sum
+    AdderFramerFeature *feat;     // the features, in stream order
+    int32_t *feat_w;              // frames_written of the period each one lies in
+};
+
 size_t viz_temp_bytes(uint64_t n);
 // n <= INT32_MAX - 1.  Queues keys, both sorts, the walk, coverage, the scans and the schedule on `stream`.  The caller
 // reads VizScalars, pops and flushed afterwards.  Changes no carried state.
+// With det.plane set it also queues the walk's detection arm, the candidates and, behind the schedule, the features
+// with their periods (det.feat, det.feat_w, VizScalars::n_feat).
 hipError_t viz_prepare(const VizArgs &a, int source, const void *d_in, uint64_t n, int32_t w0, int32_t m0, int has_limit,
-                       uint32_t limit, int opening, int finish, VizScratch &s, hipStream_t stream);
+                       uint32_t limit, int opening, int finish, VizScratch &s, const VizDetect &det, hipStream_t stream);
 // Writes the call's n_pops frames in `form`, then commits: running frame, pending ring, counts, trackers, unit state.
+// stamps: the call's n_stamps cross stamps (viz_stamp_key, sorted; device memory), painted into the running frame.
+// With det.plane set the plane is committed too.
 hipError_t viz_handout_commit(const VizArgs &a, uint64_t n, uint64_t lim, int32_t w0, uint32_t n_pops, int form,
-                              uint8_t *d_frames, const VizScratch &s, hipStream_t stream);
+                              uint8_t *d_frames, const VizScratch &s, const unsigned long long *stamps, uint32_t n_stamps,
+                              const VizDetect &det, hipStream_t stream);
 
 }  // namespace adder

@@ -60,9 +60,44 @@
  *     the framer's message (raise ring_frames); nothing changes.
  *   - wire input stops at an EOF record (x == y == 0xFFFF) or an undecodable record: *n_consumed = the records before
  *     it; the caller then calls finish.
- *   - not built: detect_features with a buffer limit (pop_features' deque bookkeeping reads frames_written at every
- *     event), the overlay crosses of adder.rs:359-388, u16 / u32 frames, compressed input, changing the view
- *     mid-stream.
+ *   - not built: u16 / u32 frames, compressed input, changing the view mid-stream.
+ *
+ * Feature detection (adder_viz_player_detect_features; adder.rs:281-282, 359-388 over driver.rs:482-553, 851-873).
+ * With detection on every event writes running_intensities[y][x][c] = its unit's last intensity and, when its t differs
+ * from the t ingest_event_for_chunk left in the previous event, is on channel 0 / None and 3 pixels off the border, is
+ * tested with FAST 9_16 on the plane as it stands (adder_framer.h has the per-event rules).  None of that depends on
+ * frames_written: an event that is late and dropped for its frame still writes the plane and is still tested.  The pop
+ * schedule enters in three places:
+ *   - `consume` sets last_event = None when it is entered (adder.rs:409): the first event of every period -- the event
+ *     after each distinct P_j, and the first event after set_buffer_limit or detect_features -- is never tested.  It
+ *     still writes the plane.
+ *   - A feature is filed (driver.rs:497-549) under the frames_written of the period its event lies in, from the RAW
+ *     event.t (a delta in a DeltaT stream: restated, not fixed), in u32 arithmetic that wraps.
+ *   - Every popped frame takes one FeatureInterval (pop_features, adder.rs:359), detection on or off: the deque runs
+ *     from creation.  Its features are painted into running_frame after the frame's Some values as crosses of 255:
+ *     radius 2, the vertical and the horizontal arm, every channel of the pixel.  A cross wins over that frame's value
+ *     and stays across later Nones until a Some overwrites it.  ADDER_VIZ_FRAME_RUNNING frames and
+ *     adder_viz_player_running_frame carry the crosses (the context's running frame holds them whichever form a call
+ *     asked for); ADDER_VIZ_FRAME_POPPED frames do not.
+ * The carried last event is valid unless the previous call's last consumed event ended a period, the limit or
+ * detection was set since, or the context was reset: any split of a stream into calls gives the same features,
+ * intervals and frames.  A call that is refused (frames that do not fit, a unit past the ring) changes none of the
+ * plane, the carried event, the deque and the crosses; a bad event at index b commits them as if the batch had ended
+ * before b.  With detection on a call waits for its stream once more (to read the features back) and takes fewer
+ * than 2^31 events, as without.  With detection never switched on every entry point launches what it launched before
+ * this block existed.
+ * Where the reference would index past the deque and panic, or grow it by more than 2^22 intervals for one feature,
+ * that feature and every later one is not filed (adder_viz_player_features still lists them) and
+ * adder_viz_player_frame_features reports ADDER_E_BAD_PARAMS with the reason from then on, its outputs still filled;
+ * framing and the pops of intervals go on, adder_viz_player_reset clears the state.  The panic is reached where
+ * (time / tpf + 1) * tpf wraps u32 while the unit stays inside the frame ring, i.e. for tpf > 2^32 / ring_frames: at
+ * tpf 2^17 and ring_frames 65536 an event with t = 0xFFFFFFFF reaches frame 32767, its interval end wraps to 0, the
+ * deque does not grow and the index lies past it.  Not reached through this interface: growth by 2^22 intervals (the
+ * unit would be 2^22 frames ahead, the ring holds at most 65536: refused, nothing changes) and the raised end_ts of
+ * driver.rs:544-547 (every pop takes an interval, so the deque's front always ends at (frames_written + 1) * tpf and
+ * interval idx ends at or after `time`).
+ * A call that fails with ADDER_E_HIP after its checks (an allocation, a copy or a launch inside the hand-out) leaves
+ * the context unusable: destroy it.  Not built: EventCoordless frames, detection across row bands.
  *
  * Frames are [n][height][width][channels] u8 in one of two forms:
  *   ADDER_VIZ_FRAME_POPPED   the popped frame with None as 0: the bytes of the reference's write_frame_bytes;
@@ -75,6 +110,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "adder_framer.h" /* AdderFramerFeature */
 #include "adder_hip.h"
 
 #ifdef __cplusplus
@@ -142,6 +178,33 @@ int adder_viz_player_finish(AdderVizPlayer *pl, int form, uint8_t *frames, uint6
                             int64_t *pop_index);
 /* The running_frame as it stands (host memory). */
 int adder_viz_player_running_frame(AdderVizPlayer *pl, uint8_t *frame);
+
+/* Framer::detect_features.  May be switched between any two calls; every call of it clears the carried last event (a
+ * UI update lies between two `consume` calls). */
+int adder_viz_player_detect_features(AdderVizPlayer *pl, int on);
+/* The features of the last ingest call that was not refused, in stream order (finish and refused calls leave the list
+ * as it was; reset empties it); `index` is the global stream index of the event (as in pop_index).  *count exceeding
+ * `capacity`: ADDER_E_OUT_CAPACITY, nothing is copied. */
+int adder_viz_player_features(AdderVizPlayer *pl, AdderFramerFeature *out, uint64_t capacity, uint64_t *count);
+/* One FeatureInterval per frame popped by the last ingest / finish call: end_ts[j] (room for that call's *n_frames) and
+ * the {x, y} pairs xy[2 * offsets[j] .. 2 * offsets[j + 1]) (offsets: room for *n_frames + 1).  *n_pairs exceeding
+ * xy_capacity: ADDER_E_OUT_CAPACITY, nothing is copied.  A refused call leaves the previous call's intervals. */
+int adder_viz_player_frame_features(AdderVizPlayer *pl, uint64_t *end_ts, uint64_t *offsets, uint16_t *xy,
+                                    uint64_t xy_capacity, uint64_t *n_pairs);
+/* FrameSequence::get_running_intensities: the [height][width][channels] u8 plane.  Zeros at create and reset, changed
+ * only by calls made with detection on. */
+int adder_viz_player_running_intensities(AdderVizPlayer *pl, uint8_t *out);
+int adder_viz_player_running_intensities_device(AdderVizPlayer *pl, uint8_t *d_out, void *stream);
+
+/* Where the schedule meets detection, on the host, for self-tests (the functions the kernels run): pops[k] = the local
+ * index of the event after which the k-th frame is popped, non-decreasing.  mark_out[i] = mark[i] unless event i is the
+ * first of a period; w_out[i] = w0 + the number of pops before event i. */
+int adder_viz_features_host(const int32_t *pops, uint32_t n_pops, uint64_t n, const uint8_t *mark, int32_t w0,
+                            uint8_t *mark_out, int32_t *w_out);
+/* The hand-out's running-frame rule: some / val are the popped frames [n_pops][units], stamps the sorted cross stamps
+ * ((unit << 32) | frame k); `running` is read and left as the context's running frame, frames = the RUNNING form. */
+int adder_viz_overlay_host(uint32_t units, uint32_t n_pops, const uint8_t *some, const uint8_t *val,
+                           const uint64_t *stamps, uint32_t n_stamps, uint8_t *running, uint8_t *frames);
 
 /* The pop schedule on the host, for self-tests: the arithmetic the schedule kernel runs (coverage counts per row and
  * pending frame, forced events by a search in a row-ordered prefix maximum, the period loop), on one whole stream fed

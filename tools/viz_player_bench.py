@@ -9,7 +9,11 @@ input events, frames, best of REPS wall times (the call returns after the device
 With PROFILE=<dir> the tool starts itself once more under `rocprofv3 --kernel-trace --stats` (a fresh process, one
 limit, one call, one repetition) and prints the kernel split it finds in <dir>.
 
-    python tools/viz_player_bench.py          # env: W, H, T, REPS, LIMITS=60,2, CASES=one,batches,framer,player, RING, OUT
+With DETECT=1 the viz player's feature detection is on (adder_viz_player_detect_features): the cases are named so, and
+every call also finds, files and paints the features.
+
+    python tools/viz_player_bench.py          # env: W, H, T, REPS, LIMITS=60,2, CASES=one,batches,framer,player, RING, OUT,
+                                              #      DETECT
 """
 import csv
 import glob
@@ -36,6 +40,8 @@ TPS, REF, DTM = 7650, 255, 255
 # pending frames kept: the round-up of a framed stream moves a unit one source frame ahead per EVENT, so a pixel that fires
 # k times per frame runs k * T frames ahead inside one call (rings of T + 8 and 4 * T + 8 were refused for the whole clip)
 RING = int(E.get("RING", 16 * T + 8))
+DETECT = int(E.get("DETECT", 0))
+TAG = ", detection on" if DETECT else ""
 lines = []
 
 
@@ -85,9 +91,11 @@ def main():
     for limit in LIMITS:
         hp = viz_player.HipVizPlayer(W, H, 1, tps=TPS, ref_interval=REF, delta_t_max=DTM, output_fps=fps, codec_version=2,
                                      buffer_limit=limit, ring_frames=RING, form="running")
+        if DETECT:
+            hp.detect_features(True)
         if "one" in CASES:
             s, k = timed(lambda: len(hp.ingest(ev, max_frames=RING)), hp.reset)
-            emit(case=f"{W}x{H} gray x {T}, limit {limit}, one call", events_in=n, frames=k, ms=s * 1e3,
+            emit(case=f"{W}x{H} gray x {T}, limit {limit}, one call{TAG}", events_in=n, frames=k, ms=s * 1e3,
                  events_per_s=n / s)
         if "batches" in CASES:
             def batched():
@@ -97,7 +105,7 @@ def main():
                     m += len(hp.ingest(ev[12 * a:12 * b], max_frames=RING))
                 return m
             s, k = timed(batched, hp.reset)
-            emit(case=f"{W}x{H} gray x {T}, limit {limit}, 60-frame batches", events_in=n, frames=k, ms=s * 1e3,
+            emit(case=f"{W}x{H} gray x {T}, limit {limit}, 60-frame batches{TAG}", events_in=n, frames=k, ms=s * 1e3,
                  events_per_s=n / s)
         hp.close()
         torch.cuda.empty_cache()
