@@ -28,12 +28,14 @@ from . import player as _player
 from .player import HipPlayer, play_file  # noqa: F401
 from . import viz_player as _viz_player
 from .viz_player import HipVizPlayer, viz_play_file  # noqa: F401
+from . import color as _color
+from .color import to_gray_device, to_gray_host  # noqa: F401
 
 
 def load():
     """Loads libadder_hip.so and binds every symbol include/adder_hip.h, adder_framer.h, adder_compressed.h,
-    adder_dvs.h, adder_quality.h, adder_prophesee.h, adder_stream.h, adder_player.h and adder_viz_player.h declare; raises if one
-    is missing."""
+    adder_dvs.h, adder_quality.h, adder_prophesee.h, adder_stream.h, adder_player.h, adder_viz_player.h and adder_color.h declare;
+    raises if one is missing."""
     L = _native.load()
     _dvs.load()
     _prophesee.load()
@@ -41,4 +43,5 @@ def load():
     _stream_tools.load()
     _player.load()
     _viz_player.load()
+    _color.load()
     return L

@@ -380,6 +380,61 @@ class HipVideo:
             self.h, d_frames.data_ptr(), T, ts, d_wire.data_ptr(), d_wire.numel() * d_wire.element_size(), d_offsets.data_ptr(),
             C.c_void_p(stream) if stream else None))
 
+    # ---- colour frames into a one-channel context (include/adder_hip.h, the *_rgb entry points) ----------
+    def _rgb_device_args(self, d_rgb_frames, d_offsets):
+        T = d_rgb_frames.shape[0]
+        assert d_rgb_frames.is_contiguous() and d_rgb_frames.numel() == T * self.n_units * 3
+        assert d_offsets.numel() >= T + 1 and d_offsets.element_size() == 8
+        return T
+
+    def integrate_rgb_device(self, d_rgb_frames, d_events, d_offsets, time_spanned=None, stream=None):
+        """integrate_device for colour frames: d_rgb_frames is a uint8 CUDA tensor [T, rows, width, 3]; the context
+        converts it to gray on the batch's stream (adder_color.h) in front of the batch."""
+        T = self._rgb_device_args(d_rgb_frames, d_offsets)
+        cap = d_events.numel() * d_events.element_size() // 12
+        ts = float(self.ref_time) if time_spanned is None else float(time_spanned)
+        N.check(self.h, self.L.adder_hip_integrate_rgb_device(
+            self.h, d_rgb_frames.data_ptr(), T, ts, d_events.data_ptr(), cap, d_offsets.data_ptr(),
+            C.c_void_p(stream) if stream else None))
+
+    def integrate_wire_rgb_device(self, d_rgb_frames, d_wire, d_offsets, time_spanned=None, stream=None):
+        """integrate_wire_device for colour frames (uint8 CUDA tensor [T, rows, width, 3])."""
+        T = self._rgb_device_args(d_rgb_frames, d_offsets)
+        ts = float(self.ref_time) if time_spanned is None else float(time_spanned)
+        N.check(self.h, self.L.adder_hip_integrate_wire_rgb_device(
+            self.h, d_rgb_frames.data_ptr(), T, ts, d_wire.data_ptr(), d_wire.numel() * d_wire.element_size(), d_offsets.data_ptr(),
+            C.c_void_p(stream) if stream else None))
+
+    def integrate_batch_rgb(self, frames, time_spanned=None, out_cap=None):
+        """integrate_batch for colour frames: a host array [T, rows, width, 3] (a view with padded rows / frames is passed
+        with its strides) -> (events, frame_offsets[T+1])."""
+        frames = np.asarray(frames, dtype=np.uint8)
+        T = frames.shape[0]
+        if frames.shape != (T, self.rows, self.width, 3) or frames.strides[3] != 1 or frames.strides[2] != 3 \
+                or min(frames.strides) < 0:
+            frames = np.ascontiguousarray(frames).reshape(T, self.rows, self.width, 3)
+        ts = float(self.ref_time) if time_spanned is None else float(time_spanned)
+        cap = min(self.max_events_per_frame, 4 * self.n_units) * T if out_cap is None else out_cap
+        out = self._host_out(cap)
+        n = C.c_size_t(0)
+        offs = np.zeros(T + 1, np.uint64)
+        rc = self.L.adder_hip_integrate_batch_rgb(self.h, frames.ctypes.data, T, frames.strides[0] if T > 1 else 0,
+                                                  frames.strides[1] if self.rows > 1 else 0, ts, out.ctypes.data, cap,
+                                                  C.byref(n), offs.ctypes.data)
+        self.last_required = n.value
+        N.check(self.h, rc)
+        return _copy_events(out, n.value), offs
+
+    def frame_submit_rgb(self, frame, time_spanned=None):
+        """frame_submit for a colour frame [rows, width, 3] (padded rows are passed with their stride); collected with
+        frame_collect / frame_collect_wire."""
+        frame = np.asarray(frame, dtype=np.uint8)
+        if frame.shape != (self.rows, self.width, 3) or frame.strides[2] != 1 or frame.strides[1] != 3 or frame.strides[0] < 0:
+            frame = np.ascontiguousarray(frame).reshape(self.rows, self.width, 3)
+        ts = float(self.ref_time) if time_spanned is None else float(time_spanned)
+        N.check(self.h, self.L.adder_hip_frame_submit_rgb(self.h, frame.ctypes.data, frame.strides[0] if self.rows > 1 else 0, ts))
+        self._inflight = getattr(self, "_inflight", []) + [frame]  # keep the source alive until it is collected
+
     # ---- records over the wire (include/adder_hip.h): a band ships its parked records, root expands them ----
     def band_segments(self):
         return int(self.L.adder_hip_band_segments(self.h))

@@ -13,6 +13,7 @@
 
 #include <new>
 
+#include "adder_color_kernels.h"
 #include "adder_hip_ctx.hpp"
 
 static_assert(sizeof(AdderEvent) == 12, "AdderEvent must be 12 bytes");
@@ -44,7 +45,7 @@ static void free_ctx(AdderHipCtx *c) {
     void *ptrs[] = {c->state_slab, c->dv_integ, c->dv_dt,
                     c->dv_bdt,  c->dv_bd,   c->running_base, c->d_new_xy, c->cn_integ, c->cn_dt, c->cn_bdt, c->cn_meta,
                     c->snap.cn_integ, c->snap.cn_dt, c->snap.cn_bdt, c->snap.cn_meta,
-                    c->d_offsets, c->d_frames, c->d_events, c->d_chunks, c->d_wire,
+                    c->d_offsets, c->d_frames, c->d_rgb, c->d_events, c->d_chunks, c->d_wire,
                     c->cth_px, c->cctr_px, c->fset, c->fstamp, c->d_display, c->own.feat_counters, c->snap.cth_px, c->snap.cctr_px, c->snap.fset,
                     c->snap.fstamp,
                     c->snap.running};
@@ -62,7 +63,7 @@ static void free_ctx(AdderHipCtx *c) {
     }
     for (auto &fs : c->fslot) {
         if (fs.out_graph) (void)hipGraphExecDestroy(fs.out_graph);
-        for (void *p : {(void *)fs.d_frame, (void *)fs.d_events, (void *)fs.d_offsets, (void *)fs.desc.d_batch,
+        for (void *p : {(void *)fs.d_frame, (void *)fs.d_rgb, (void *)fs.d_events, (void *)fs.d_offsets, (void *)fs.desc.d_batch,
                         (void *)fs.desc.feat_counters})
             if (p) (void)hipFree(p);
         for (void *p : {(void *)fs.h_events, (void *)fs.h_hdr, (void *)fs.desc.h_batch})
@@ -428,9 +429,20 @@ int join_null_stream(AdderHipCtx *c) {
     return ADDER_OK;
 }
 
+// the *_rgb entry points exist for one-channel contexts only (a colour context takes the colour frame as it is)
+int rgb_precheck(AdderHipCtx *c) {
+    if (c->p.channels != 1)
+        return fail(c, ADDER_E_BAD_PARAMS, "colour frames are converted for a channels == 1 context only (this one has %u "
+                    "channels and takes them as they are)", c->p.channels);
+    return ADDER_OK;
+}
+
 // A device batch into AdderEvents, or (wire) into the raw sink's records: d_out then holds bytes, out_cap counts records.
+// rgb: d_frames holds [num_frames][rows][width][3]; the batch reads their gray form (adder_color.hip) out of c->d_frames.
+// The conversion goes on the batch's stream in front of it -- behind the NULL-stream join, outside the captured graphs --
+// and c->d_frames is not written again before the batch has been finished: the next batch is refused until then.
 static int integrate_device(AdderHipCtx *c, const uint8_t *d_frames, uint32_t num_frames, float time_spanned, AdderEvent *d_out,
-                            size_t out_cap, uint64_t *d_frame_offsets, void *stream, bool wire) {
+                            size_t out_cap, uint64_t *d_frame_offsets, void *stream, bool wire, bool rgb = false) {
     if (c->poisoned) return refuse_poisoned(c);
     if (c->pending) return fail(c, ADDER_E_BAD_PARAMS, "previous device batch not finished (call adder_hip_finish)");
     if (c->f_submitted != c->f_collected)
@@ -444,6 +456,14 @@ static int integrate_device(AdderHipCtx *c, const uint8_t *d_frames, uint32_t nu
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     if (!stream) ADDER_TRY(join_null_stream(c));
+    if (rgb && num_frames != 0) {
+        void *vp = c->d_frames;
+        ADDER_TRY(ensure(c, &vp, &c->d_frames_cap, (size_t)num_frames * c->n_units + 16));
+        c->d_frames = (uint8_t *)vp;
+        HIPCHK(c, color_to_gray_launch(d_frames, (uint64_t)c->p.width * 3u, (uint64_t)c->n_units * 3u, c->d_frames, c->p.width,
+                                       c->n_units, c->p.width, c->rows, num_frames, s));
+        d_frames = c->d_frames;
+    }
     if (num_frames == 0) {
         HIPCHK(c, hipMemsetAsync(d_frame_offsets, 0, sizeof(uint64_t), s));
     } else {
@@ -485,6 +505,22 @@ extern "C" int adder_hip_integrate_wire_device(AdderHipCtx *c, const uint8_t *d_
     if (!c) return ADDER_E_BAD_PARAMS;
     return integrate_device(c, d_frames, num_frames, time_spanned, reinterpret_cast<AdderEvent *>(d_wire),
                             wire_cap_bytes / wire_record_bytes(c), d_frame_offsets, stream, true);
+}
+
+extern "C" int adder_hip_integrate_rgb_device(AdderHipCtx *c, const uint8_t *d_rgb_frames, uint32_t num_frames, float time_spanned,
+                                              AdderEvent *d_out, size_t out_cap, uint64_t *d_frame_offsets, void *stream) {
+    if (!c) return ADDER_E_BAD_PARAMS;
+    ADDER_TRY(rgb_precheck(c));
+    return integrate_device(c, d_rgb_frames, num_frames, time_spanned, d_out, out_cap, d_frame_offsets, stream, false, true);
+}
+
+extern "C" int adder_hip_integrate_wire_rgb_device(AdderHipCtx *c, const uint8_t *d_rgb_frames, uint32_t num_frames,
+                                                   float time_spanned, uint8_t *d_wire, size_t wire_cap_bytes,
+                                                   uint64_t *d_frame_offsets, void *stream) {
+    if (!c) return ADDER_E_BAD_PARAMS;
+    ADDER_TRY(rgb_precheck(c));
+    return integrate_device(c, d_rgb_frames, num_frames, time_spanned, reinterpret_cast<AdderEvent *>(d_wire),
+                            wire_cap_bytes / wire_record_bytes(c), d_frame_offsets, stream, true, true);
 }
 
 extern "C" void *adder_hip_last_batch_stream(AdderHipCtx *c) {
@@ -655,21 +691,24 @@ int ensure(AdderHipCtx *c, void **p, size_t *cap, size_t need) {
 
 // Host frames -> device, integrate, finish: the events of the batch end up in c->d_events
 // (capacity out_cap events), the frame offsets in c->d_offsets; *total = number of events.
+// rgb: the frames are [rows][width][3]; they are uploaded to c->d_rgb and the batch converts them (integrate_device).
 int batch_to_device(AdderHipCtx *c, const uint8_t *frames, uint32_t num_frames, size_t frame_stride, size_t row_stride,
-                    float time_spanned, size_t out_cap, size_t *total) {
+                    float time_spanned, size_t out_cap, size_t *total, bool rgb) {
     *total = 0;
     if (c->poisoned) return refuse_poisoned(c);
     if (c->pending) return fail(c, ADDER_E_BAD_PARAMS, "a device batch is pending (call adder_hip_finish)");
     if (!frames && num_frames) return fail(c, ADDER_E_BAD_PARAMS, "frames is null");
-    const size_t rowlen = (size_t)c->p.width * c->p.channels;
+    const size_t rowlen = (size_t)c->p.width * (rgb ? 3u : c->p.channels);
+    const size_t frame_bytes = rowlen * c->rows;  // (gray: n_units)
     if (row_stride == 0) row_stride = rowlen;
     if (row_stride < rowlen) return fail(c, ADDER_E_BAD_PARAMS, "row_stride_bytes smaller than a row");
     if (frame_stride == 0) frame_stride = row_stride * c->rows;
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    void *vp = c->d_frames;
-    if ((rc = ensure(c, &vp, &c->d_frames_cap, (size_t)num_frames * c->n_units + 16)) != ADDER_OK) return rc;
-    c->d_frames = (uint8_t *)vp;
+    void *vp = rgb ? c->d_rgb : c->d_frames;
+    if ((rc = ensure(c, &vp, rgb ? &c->d_rgb_cap : &c->d_frames_cap, (size_t)num_frames * frame_bytes + 16)) != ADDER_OK) return rc;
+    (rgb ? c->d_rgb : c->d_frames) = (uint8_t *)vp;
+    uint8_t *const d_in = (uint8_t *)vp;
     vp = c->d_events;
     if ((rc = ensure(c, &vp, &c->d_events_cap, out_cap * sizeof(AdderEvent))) != ADDER_OK) return rc;
     c->d_events = (AdderEvent *)vp;
@@ -677,18 +716,33 @@ int batch_to_device(AdderHipCtx *c, const uint8_t *frames, uint32_t num_frames, 
     if ((rc = ensure(c, &vp, &c->d_offsets_cap, ((size_t)num_frames + 1) * sizeof(uint64_t))) != ADDER_OK) return rc;
     c->d_offsets = (uint64_t *)vp;
 
-    if (row_stride == rowlen && frame_stride == rowlen * c->rows) {  // packed: one linear copy
-        HIPCHK(c, hipMemcpyAsync(c->d_frames, frames, (size_t)num_frames * c->n_units, hipMemcpyHostToDevice, c->stream));
+    if (row_stride == rowlen && frame_stride == frame_bytes) {  // packed: one linear copy
+        HIPCHK(c, hipMemcpyAsync(d_in, frames, (size_t)num_frames * frame_bytes, hipMemcpyHostToDevice, c->stream));
     } else {
         for (uint32_t f = 0; f < num_frames; ++f)
-            HIPCHK(c, hipMemcpy2DAsync(c->d_frames + (size_t)f * c->n_units, rowlen, frames + (size_t)f * frame_stride,
+            HIPCHK(c, hipMemcpy2DAsync(d_in + (size_t)f * frame_bytes, rowlen, frames + (size_t)f * frame_stride,
                                        row_stride, rowlen, c->rows, hipMemcpyHostToDevice, c->stream));
     }
-    rc = adder_hip_integrate_device(c, c->d_frames, num_frames, time_spanned, c->d_events, out_cap, c->d_offsets,
-                                    c->stream);
+    rc = integrate_device(c, d_in, num_frames, time_spanned, c->d_events, out_cap, c->d_offsets, c->stream, false, rgb);
     if (rc != ADDER_OK) return rc;
     rc = adder_hip_finish(c, total);
     if (rc != ADDER_OK) return rc;  // ADDER_E_OUT_CAPACITY: rolled back, *total = the size needed
+    return ADDER_OK;
+}
+
+static int integrate_batch(AdderHipCtx *c, const uint8_t *frames, uint32_t num_frames, size_t frame_stride, size_t row_stride,
+                           float time_spanned, AdderEvent *out, size_t out_cap, size_t *n_out, uint64_t *frame_offsets, bool rgb) {
+    if (n_out) *n_out = 0;
+    if (rgb) ADDER_TRY(rgb_precheck(c));
+    if (!out && out_cap) return fail(c, ADDER_E_BAD_PARAMS, "out is null");
+    size_t total = 0;
+    int rc = batch_to_device(c, frames, num_frames, frame_stride, row_stride, time_spanned, out_cap, &total, rgb);
+    if (n_out) *n_out = total;
+    if (rc != ADDER_OK) return rc;
+    if (total) HIPCHK(c, hipMemcpy(out, c->d_events, total * sizeof(AdderEvent), hipMemcpyDeviceToHost));
+    if (frame_offsets)
+        HIPCHK(c, hipMemcpy(frame_offsets, c->d_offsets, ((size_t)num_frames + 1) * sizeof(uint64_t),
+                            hipMemcpyDeviceToHost));
     return ADDER_OK;
 }
 
@@ -697,17 +751,14 @@ extern "C" int adder_hip_integrate_batch(AdderHipCtx *c, const uint8_t *frames, 
                                          AdderEvent *out, size_t out_cap, size_t *n_out,
                                          uint64_t *frame_offsets) {
     if (!c) return ADDER_E_BAD_PARAMS;
-    if (n_out) *n_out = 0;
-    if (!out && out_cap) return fail(c, ADDER_E_BAD_PARAMS, "out is null");
-    size_t total = 0;
-    int rc = batch_to_device(c, frames, num_frames, frame_stride, row_stride, time_spanned, out_cap, &total);
-    if (n_out) *n_out = total;
-    if (rc != ADDER_OK) return rc;
-    if (total) HIPCHK(c, hipMemcpy(out, c->d_events, total * sizeof(AdderEvent), hipMemcpyDeviceToHost));
-    if (frame_offsets)
-        HIPCHK(c, hipMemcpy(frame_offsets, c->d_offsets, ((size_t)num_frames + 1) * sizeof(uint64_t),
-                            hipMemcpyDeviceToHost));
-    return ADDER_OK;
+    return integrate_batch(c, frames, num_frames, frame_stride, row_stride, time_spanned, out, out_cap, n_out, frame_offsets, false);
+}
+
+extern "C" int adder_hip_integrate_batch_rgb(AdderHipCtx *c, const uint8_t *frames_hwc3, uint32_t num_frames, size_t frame_stride,
+                                             size_t row_stride, float time_spanned, AdderEvent *out, size_t out_cap,
+                                             size_t *n_out, uint64_t *frame_offsets) {
+    if (!c) return ADDER_E_BAD_PARAMS;
+    return integrate_batch(c, frames_hwc3, num_frames, frame_stride, row_stride, time_spanned, out, out_cap, n_out, frame_offsets, true);
 }
 
 extern "C" int adder_hip_integrate_batch_raw(AdderHipCtx *c, const uint8_t *frames, uint32_t num_frames,

@@ -203,8 +203,10 @@ struct AdderHipCtx {
     uint64_t *d_offsets = nullptr;  // internal frame offsets (host-buffer API)
     size_t d_offsets_cap = 0;       // all *_cap below are in BYTES
     // staging for the host-buffer API
-    uint8_t *d_frames = nullptr;
+    uint8_t *d_frames = nullptr;    // ... and the gray form of a colour batch (the *_rgb entry points, device and host)
     size_t d_frames_cap = 0;
+    uint8_t *d_rgb = nullptr;       // adder_hip_integrate_batch_rgb: the colour frames as they were uploaded
+    size_t d_rgb_cap = 0;
     AdderEvent *d_events = nullptr;
     size_t d_events_cap = 0;
     uint8_t *d_wire = nullptr;      // wire-format bytes of the last raw batch
@@ -230,6 +232,7 @@ struct AdderHipCtx {
     // by the DMA engine after submit has returned)
     struct FrameSlot {
         uint8_t *d_frame = nullptr;
+        uint8_t *d_rgb = nullptr;       // adder_hip_frame_submit_rgb: the colour frame, converted into d_frame on the upload stream
         AdderEvent *d_events = nullptr, *h_events = nullptr;
         size_t cap = 0;                 // events
         uint8_t *h_hdr = nullptr;       // pinned: FrameResult, then chunk offsets [num_chunks + 1]
@@ -315,9 +318,10 @@ int fail(AdderHipCtx *ctx, int code, const char *fmt, ...);
 int refuse_poisoned(AdderHipCtx *c);  // ADDER_E_POISONED with the earlier failure's message
 int status_to_code(AdderHipCtx *c, uint32_t st);
 int join_null_stream(AdderHipCtx *c);
+int rgb_precheck(AdderHipCtx *c);  // ADDER_E_BAD_PARAMS unless the context has one channel (the *_rgb entry points)
 int ensure(AdderHipCtx *c, void **p, size_t *cap, size_t need);
 int batch_to_device(AdderHipCtx *c, const uint8_t *frames, uint32_t num_frames, size_t frame_stride, size_t row_stride,
-                    float time_spanned, size_t out_cap, size_t *total);
+                    float time_spanned, size_t out_cap, size_t *total, bool rgb = false);
 // adder_hip_batch.cpp
 StepConsts make_consts(const AdderHipCtx *c, float time_spanned);
 ViewConsts make_view(const AdderHipCtx *c);
@@ -339,7 +343,7 @@ int join_ri_copy(AdderHipCtx *c, hipStream_t s);
 FeatureArgs feature_args(const AdderHipCtx *c, const BatchDesc &desc);
 // adder_hip_ring_api.cpp
 int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_stride, float time_spanned, AdderEvent *direct_out,
-                      size_t direct_cap);
+                      size_t direct_cap, bool rgb = false);
 int frame_collect_impl(AdderHipCtx *c, const AdderEvent **events, size_t *n_events, const uint32_t **chunk_offsets);
 #pragma GCC visibility pop
 

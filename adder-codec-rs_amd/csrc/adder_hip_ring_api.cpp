@@ -3,6 +3,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "adder_color_kernels.h"
 #include "adder_hip_ctx.hpp"
 
 static int ensure_pinned(AdderHipCtx *c, void **p, size_t *cap, size_t need) {
@@ -128,8 +129,10 @@ static uint32_t wire_scatter_blocks(const AdderHipCtx *c) {
     return env ? env : c->num_cus * 2u;  // (sweep, 1080p e = 0.3: 64-128: 203, 256: 197, 512: 185, 1024: 189 us per frame)
 }
 
+// rgb: `frame` is [rows][width][3] for a one-channel context.  It is uploaded into the slot's colour staging frame and
+// converted into the slot's gray frame (adder_color.hip) on the upload stream, in front of the event the frame kernel waits for.
 int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_stride, float time_spanned, AdderEvent *direct_out,
-                      size_t direct_cap) {
+                      size_t direct_cap, bool rgb) {
     if (c->poisoned) return refuse_poisoned(c);
     if (c->pending) return fail(c, ADDER_E_BAD_PARAMS, "a device batch is pending (call adder_hip_finish)");
     if (c->submitted != c->collected) return fail(c, ADDER_E_BAD_PARAMS, "a raw stream batch is in flight");
@@ -140,7 +143,7 @@ int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_stride, f
     if (band_features(c))
         return fail(c, ADDER_E_BAD_PARAMS, "a row band in feature / ROI mode uses the blocking calls (its feature step "
                     "needs the neighbours' halo between the frames)");
-    const size_t rowlen = (size_t)c->p.width * c->p.channels;
+    const size_t rowlen = (size_t)c->p.width * (rgb ? 3u : c->p.channels);
     if (row_stride == 0) row_stride = rowlen;
     if (row_stride < rowlen) return fail(c, ADDER_E_BAD_PARAMS, "row_stride_bytes smaller than a row");
     HIPCHK(c, hipSetDevice(c->device));
@@ -193,10 +196,15 @@ int frame_submit_impl(AdderHipCtx *c, const uint8_t *frame, size_t row_stride, f
         ring_out = rc_.out_s;
         post_on_main = rc_.post_on_main;
     }
+    if (rgb && !fs.d_rgb) HIPCHK(c, dalloc(&fs.d_rgb, rowlen * c->rows + 16));
+    uint8_t *const d_in = rgb ? fs.d_rgb : fs.d_frame;
     if (row_stride == rowlen)
-        HIPCHK(c, hipMemcpyAsync(fs.d_frame, frame, c->n_units, hipMemcpyHostToDevice, up));
+        HIPCHK(c, hipMemcpyAsync(d_in, frame, rowlen * c->rows, hipMemcpyHostToDevice, up));
     else
-        HIPCHK(c, hipMemcpy2DAsync(fs.d_frame, rowlen, frame, row_stride, rowlen, c->rows, hipMemcpyHostToDevice, up));
+        HIPCHK(c, hipMemcpy2DAsync(d_in, rowlen, frame, row_stride, rowlen, c->rows, hipMemcpyHostToDevice, up));
+    if (rgb)
+        HIPCHK(c, color_to_gray_launch(fs.d_rgb, rowlen, rowlen * c->rows, fs.d_frame, c->p.width, c->n_units, c->p.width, c->rows,
+                                       1u, up));
     if (own_upload) {
         HIPCHK(c, hipEventRecord(c->in_e, up));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->in_e, 0));
@@ -382,6 +390,12 @@ extern "C" int adder_hip_frames_configure(AdderHipCtx *c, uint32_t slots, size_t
 extern "C" int adder_hip_frame_submit(AdderHipCtx *c, const uint8_t *frame, size_t row_stride, float time_spanned) {
     if (!c) return ADDER_E_BAD_PARAMS;
     return frame_submit_impl(c, frame, row_stride, time_spanned, nullptr, 0);
+}
+
+extern "C" int adder_hip_frame_submit_rgb(AdderHipCtx *c, const uint8_t *frame_hwc3, size_t row_stride, float time_spanned) {
+    if (!c) return ADDER_E_BAD_PARAMS;
+    ADDER_TRY(rgb_precheck(c));
+    return frame_submit_impl(c, frame_hwc3, row_stride, time_spanned, nullptr, 0, true);
 }
 
 extern "C" int adder_hip_frame_collect(AdderHipCtx *c, const AdderEvent **events, size_t *n_events,

@@ -546,13 +546,26 @@ void Video::ensure_ctx() {
 std::vector<std::vector<Event>> Video::integrate_matrix(const Frame &matrix, float time_spanned) {
     if (matrix.size() != plane_.volume())
         throw SourceError(SourceError::BadParams, "frame does not match the plane");
+    return integrate_one(matrix.data(), false, time_spanned);
+}
+
+std::vector<std::vector<Event>> Video::integrate_matrix_rgb(const Frame &rgb, float time_spanned) {
+    if (plane_.c() != 1 || rgb.size() != plane_.volume() * 3)
+        throw SourceError(SourceError::BadParams, "a colour frame [h][w][3] for a one-channel plane");
+    return integrate_one(rgb.data(), true, time_spanned);
+}
+
+std::vector<std::vector<Event>> Video::integrate_one(const uint8_t *frame, bool rgb, float time_spanned) {
     ensure_ctx();
     // in_interval_count starts at 1 (video.rs:231), so set_initial_d (:656-658) is never taken here
     in_interval_count_ += 1;
     const uint32_t num_chunks = adder_hip_num_chunks(ctx_);
     // one frame through the ring: the events come back as a view of a page-locked slot that holds the mode's
     // worst case, so nothing can overflow and nothing is copied before the per-chunk vectors are built
-    hip_check(ctx_, adder_hip_frame_submit(ctx_, matrix.data(), (size_t)plane_.w() * plane_.c(), time_spanned));
+    if (rgb)  // (the ring converts the colour frame on its upload stream: adder_hip.h)
+        hip_check(ctx_, adder_hip_frame_submit_rgb(ctx_, frame, (size_t)plane_.w() * 3, time_spanned));
+    else
+        hip_check(ctx_, adder_hip_frame_submit(ctx_, frame, (size_t)plane_.w() * plane_.c(), time_spanned));
     const AdderEvent *ev = nullptr;
     const uint32_t *offs = nullptr;
     size_t n = 0;
@@ -926,8 +939,23 @@ std::vector<std::vector<Event>> Framed::consume() {
     Frame raw;
     if (!cap_.decode || !cap_.decode(next_frame_, raw)) throw SourceError(SourceError::NoData, "no more frames");
     ++next_frame_;
+    if (convert_on_device_ && !color_input_ && cap_.channels == 3) {
+        // the decoder's frame goes to the device as it is; its gray form is made here only when somebody asks (input())
+        raw_frame_ = std::move(raw);
+        input_stale_ = true;
+        return video_.integrate_matrix_rgb(raw_frame_, (float)video_.get_ref_time());
+    }
+    input_stale_ = false;
     input_frame_ = handle_color(raw, cap_.width, cap_.height, cap_.channels, color_input_);
     return video_.integrate_matrix(input_frame_, (float)video_.get_ref_time());
+}
+
+const Frame &Framed::input() const {
+    if (input_stale_) {
+        input_frame_ = handle_color(raw_frame_, cap_.width, cap_.height, cap_.channels, color_input_);
+        input_stale_ = false;
+    }
+    return input_frame_;
 }
 
 double Framed::get_running_input_bitrate() const {

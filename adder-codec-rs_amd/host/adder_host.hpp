@@ -238,6 +238,9 @@ class Video {
     // :651-778 -- one frame in; Vec<Vec<Event>> out (one vector per row chunk, raster order);
     // the events are also pushed through the encoder, exactly like the reference.
     std::vector<std::vector<Event>> integrate_matrix(const Frame &matrix, float time_spanned);
+    // the same for a one-channel plane fed the decoder's colour frame [h][w][3]: handle_color (utils/cv.rs:215-232)
+    // runs on the device, in front of the frame kernel (adder_hip_frame_submit_rgb)
+    std::vector<std::vector<Event>> integrate_matrix_rgb(const Frame &rgb, float time_spanned);
     // the same for T packed frames in one boundary call (events of all frames, frame-major)
     std::vector<Event> integrate_frames(const uint8_t *frames, uint32_t num_frames, float time_spanned,
                                         std::vector<uint64_t> *frame_offsets);
@@ -246,6 +249,7 @@ class Video {
     std::vector<Event> integrate_sparse(const std::vector<AdderSparseStep> &steps);
 
   private:
+    std::vector<std::vector<Event>> integrate_one(const uint8_t *frame, bool rgb, float time_spanned);
     void ensure_ctx();  // (re)creates the device context once every builder call has been made
     void sync_feature_controls();
     void sync_view_controls();
@@ -295,7 +299,11 @@ class Framed : public Source {  // framed.rs:22-39
     Framed &frame_start(uint32_t frame_idx_start);                          // :81-91
     Framed &auto_time_parameters(uint32_t ref_time, uint32_t delta_t_max, std::optional<TimeMode> time_mode);  // :94-111
     uint32_t get_ref_time() const { return video_.get_ref_time(); }
-    const Frame &get_last_input_frame() const { return input_frame_; }
+    const Frame &get_last_input_frame() const { return input(); }
+    // Opt-in (default off: consume() converts on the CPU, as it always has): a gray transcode of a 3-channel provider
+    // hands the decoder's frame to the device, which converts it bit for bit (include/adder_color.h); the gray frame
+    // behind get_input() / get_last_input_frame() is then computed on the CPU only when one of them is called.
+    Framed &convert_on_device(bool on) { convert_on_device_ = on; return *this; }
     // VideoBuilder (framed.rs:187-280)
     Framed &crf_builder(uint8_t crf) { video_.update_crf(crf); return *this; }
     Framed &quality_manual(uint8_t base, uint8_t max, uint32_t dtm_mult, uint8_t velocity, float radius) {
@@ -312,16 +320,20 @@ class Framed : public Source {  // framed.rs:22-39
     void crf(uint8_t crf) override { video_.update_crf(crf); }
     Video &get_video_mut() override { return video_; }
     const Video &get_video_ref() const override { return video_; }
-    const Frame *get_input() const override { return &input_frame_; }
+    const Frame *get_input() const override { return &input(); }
     double get_running_input_bitrate() const override;
 
     uint32_t frame_idx_start = 0;
     float source_fps;
 
   private:
+    const Frame &input() const;  // input_frame_, brought up to date from raw_frame_ first (convert_on_device)
     FrameProvider cap_;
     uint64_t next_frame_ = 0;
-    Frame input_frame_;
+    mutable Frame input_frame_;
+    Frame raw_frame_;            // convert_on_device: the colour frame consume() handed to the device last
+    mutable bool input_stale_ = false;
+    bool convert_on_device_ = false;
     bool color_input_;
     Video video_;
 };

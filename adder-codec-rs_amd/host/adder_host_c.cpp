@@ -3,6 +3,7 @@
 // test does (adder-codec-rs/src/bin/adder_simulproc.rs:170-268).  No exception crosses it.
 #include <string.h>
 
+#include <chrono>
 #include <fstream>
 #include <sstream>
 #include <string>
@@ -21,12 +22,15 @@ const char *adder_host_last_error() { return g_err.c_str(); }
 // reference's transcode test: crf -> (auto_)time_parameters -> write_out(raw, options) -> consume()
 // x T -> end_write_stream.  Returns the number of events, or -1.
 // encoder_type: 0 = Compressed (adu_interval reference intervals per ADU), 1 = Raw
-long long adder_host_transcode(const uint8_t *frames, uint32_t num_frames, uint32_t width, uint32_t height,
-                               uint32_t channels_in, int color_input, float fps, int crf /* <0: none */,
-                               uint32_t ref_time, uint32_t delta_t_max, int time_mode, int multi_mode,
-                               uint32_t chunk_rows, int encoder_crf /* <0: EncoderOptions::default */,
-                               int encoder_type, uint32_t adu_interval, const char *out_path,
-                               uint32_t *num_chunks_out) {
+// convert_on_device: Framed::convert_on_device; last_input (may be null): get_input() after the last consume(),
+// [h][w][color_input ? 3 : 1]; consume_seconds (may be null): wall-clock time of the consume() loop alone.
+static long long transcode_impl(const uint8_t *frames, uint32_t num_frames, uint32_t width, uint32_t height,
+                                uint32_t channels_in, int color_input, float fps, int crf /* <0: none */,
+                                uint32_t ref_time, uint32_t delta_t_max, int time_mode, int multi_mode,
+                                uint32_t chunk_rows, int encoder_crf /* <0: EncoderOptions::default */,
+                                int encoder_type, uint32_t adu_interval, const char *out_path,
+                                uint32_t *num_chunks_out, int convert_on_device, uint8_t *last_input,
+                                double *consume_seconds) {
     try {
         FrameProvider cap;
         cap.width = width;
@@ -41,6 +45,7 @@ long long adder_host_transcode(const uint8_t *frames, uint32_t num_frames, uint3
             return true;
         };
         Framed source(cap, color_input != 0);
+        source.convert_on_device(convert_on_device != 0);
         source.chunk_rows(chunk_rows ? chunk_rows : 1);
         if (crf >= 0) source.crf_builder((uint8_t)crf);
         source.auto_time_parameters(ref_time, delta_t_max, std::nullopt);
@@ -54,10 +59,16 @@ long long adder_host_transcode(const uint8_t *frames, uint32_t num_frames, uint3
                          encoder_type == 0 ? EncoderType::Compressed : EncoderType::Raw, opts, &file);
         long long total = 0;
         uint32_t chunks = 0;
+        const auto t0 = std::chrono::steady_clock::now();
         for (uint32_t k = 0; k < num_frames; ++k) {
             auto events = source.consume();
             chunks = (uint32_t)events.size();
             for (auto &v : events) total += (long long)v.size();
+        }
+        if (consume_seconds) *consume_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (last_input && num_frames) {
+            const Frame *in = source.get_input();
+            memcpy(last_input, in->data(), in->size());
         }
         source.get_video_mut().end_write_stream();
         if (num_chunks_out) *num_chunks_out = chunks;
@@ -66,6 +77,17 @@ long long adder_host_transcode(const uint8_t *frames, uint32_t num_frames, uint3
         g_err = e.what();
         return -1;
     }
+}
+
+long long adder_host_transcode(const uint8_t *frames, uint32_t num_frames, uint32_t width, uint32_t height,
+                               uint32_t channels_in, int color_input, float fps, int crf /* <0: none */,
+                               uint32_t ref_time, uint32_t delta_t_max, int time_mode, int multi_mode,
+                               uint32_t chunk_rows, int encoder_crf /* <0: EncoderOptions::default */,
+                               int encoder_type, uint32_t adu_interval, const char *out_path,
+                               uint32_t *num_chunks_out) {
+    return transcode_impl(frames, num_frames, width, height, channels_in, color_input, fps, crf, ref_time, delta_t_max,
+                          time_mode, multi_mode, chunk_rows, encoder_crf, encoder_type, adu_interval, out_path,
+                          num_chunks_out, 0, nullptr, nullptr);
 }
 
 // The same flow with the controls of adder-viz's transcoder tab (adder-viz/src/transcoder/adder.rs: update_crf /
@@ -273,6 +295,20 @@ long long adder_host_transcode_raw(const uint8_t *frames, uint32_t num_frames, u
     return adder_host_transcode(frames, num_frames, width, height, channels_in, color_input, fps, crf, ref_time,
                                 delta_t_max, time_mode, multi_mode, chunk_rows, encoder_crf, 1, 0, out_path,
                                 num_chunks_out);
+}
+
+// adder_host_transcode_raw with Framed::convert_on_device as an argument (0: the call above, byte for byte), the gray frame
+// behind get_input() after the last consume() (last_input: [h][w], or [h][w][3] with color_input; may be null) and the
+// wall-clock seconds of the consume() loop (may be null).
+long long adder_host_transcode_raw_ex(const uint8_t *frames, uint32_t num_frames, uint32_t width, uint32_t height,
+                                      uint32_t channels_in, int color_input, float fps, int crf /* <0: none */,
+                                      uint32_t ref_time, uint32_t delta_t_max, int time_mode, int multi_mode,
+                                      uint32_t chunk_rows, int encoder_crf /* <0: EncoderOptions::default */,
+                                      const char *out_path, uint32_t *num_chunks_out, int convert_on_device,
+                                      uint8_t *last_input, double *consume_seconds) {
+    return transcode_impl(frames, num_frames, width, height, channels_in, color_input, fps, crf, ref_time, delta_t_max,
+                          time_mode, multi_mode, chunk_rows, encoder_crf, 1, 0, out_path, num_chunks_out, convert_on_device,
+                          last_input, consume_seconds);
 }
 
 // The reference's `dark` test end to end (src/bin/adder_simulproc.rs:170-268): Framed(gray) ->

@@ -273,6 +273,31 @@ int adder_hip_integrate_device(AdderHipCtx *ctx, const uint8_t *d_frames, uint32
  * and nothing from byte (wire_cap_bytes / record_bytes) * record_bytes on is written. */
 int adder_hip_integrate_wire_device(AdderHipCtx *ctx, const uint8_t *d_frames, uint32_t num_frames, float time_spanned,
                                     uint8_t *d_wire, size_t wire_cap_bytes, uint64_t *d_frame_offsets, void *stream);
+
+/* --- Colour frames into a ONE-channel context ----------------------------------------
+ * The reference's decoder delivers three-channel frames, and a gray transcode (color_input == false, adder_simulproc's
+ * default) converts each in Framed::consume (framed.rs:127-134 -> utils/cv.rs:215-232) before integrate_matrix:
+ *     gray = (ch0 as f64 * 0.114 + ch1 as f64 * 0.587 + ch2 as f64 * 0.299) as u8
+ * The four functions below take this band's rows as [rows][width][3] u8 and do that on the device, bit for bit
+ * (adder_color.h), into storage of the context; from there on each IS its gray twin -- adder_hip_integrate_device,
+ * adder_hip_integrate_wire_device, adder_hip_integrate_batch, adder_hip_frame_submit -- with the twin's rules:
+ * capacity and rollback, poisoning, the refusals while other work is in flight, row bands, the NULL-stream rule.
+ * The conversion is queued on the batch's stream in front of the batch (the ring: on its upload stream, in front of the
+ * event the frame kernel waits for); it changes no pixel state.  The device forms read d_rgb_frames (packed
+ * [T][rows][width][3]) only until the conversion has run; the gray frames stay the context's until adder_hip_finish.
+ * A channels == 3 context refuses all four with ADDER_E_BAD_PARAMS and is left as it was. */
+int adder_hip_integrate_rgb_device(AdderHipCtx *ctx, const uint8_t *d_rgb_frames, uint32_t num_frames, float time_spanned,
+                                   AdderEvent *d_out, size_t out_cap, uint64_t *d_frame_offsets, void *stream);
+int adder_hip_integrate_wire_rgb_device(AdderHipCtx *ctx, const uint8_t *d_rgb_frames, uint32_t num_frames,
+                                        float time_spanned, uint8_t *d_wire, size_t wire_cap_bytes,
+                                        uint64_t *d_frame_offsets, void *stream);
+/* host frames; strides in bytes of the colour frames (0: packed, 3 * width per row) */
+int adder_hip_integrate_batch_rgb(AdderHipCtx *ctx, const uint8_t *frames_hwc3, uint32_t num_frames,
+                                  size_t frame_stride_bytes, size_t row_stride_bytes, float time_spanned, AdderEvent *out,
+                                  size_t out_cap, size_t *n_out, uint64_t *frame_offsets);
+/* the per-frame ring: collected with adder_hip_frame_collect / _collect_wire like any other frame */
+int adder_hip_frame_submit_rgb(AdderHipCtx *ctx, const uint8_t *frame_hwc3, size_t row_stride_bytes, float time_spanned);
+
 /* Waits for the work queued by adder_hip_integrate_device and reports its status;
  * *n_out (may be NULL) = total events of the last device batch. */
 int adder_hip_finish(AdderHipCtx *ctx, size_t *n_out);
