@@ -30,11 +30,13 @@ from . import viz_player as _viz_player
 from .viz_player import HipVizPlayer, viz_play_file  # noqa: F401
 from . import color as _color
 from .color import to_gray_device, to_gray_host  # noqa: F401
+from . import davis as _davis
+from .davis import HipDavis, davis_to_adder, davis_to_adder_file, DAVIS_EVENT_DTYPE  # noqa: F401
 
 
 def load():
     """Loads libadder_hip.so and binds every symbol include/adder_hip.h, adder_framer.h, adder_compressed.h,
-    adder_dvs.h, adder_quality.h, adder_prophesee.h, adder_stream.h, adder_player.h, adder_viz_player.h and adder_color.h declare;
+    adder_dvs.h, adder_quality.h, adder_prophesee.h, adder_stream.h, adder_player.h, adder_viz_player.h, adder_color.h and adder_davis.h declare;
     raises if one is missing."""
     L = _native.load()
     _dvs.load()
@@ -44,4 +46,5 @@ def load():
     _player.load()
     _viz_player.load()
     _color.load()
+    _davis.load()
     return L

@@ -608,6 +608,8 @@ std::vector<Event> Video::integrate_sparse(const std::vector<AdderSparseStep> &s
     return out;
 }
 
+void Video::ingest_events(const Event *events, size_t n) { encoder_->ingest_events(events, n); }
+
 // ---------------------------------------------------------------- Prophesee (prophesee.rs)
 static void mid_clamp_u8(double &frame_val, double &last_val_ln) {  // utils/cv.rs:444-449
     if (frame_val < 0.0 || frame_val > 255.0) {
@@ -798,7 +800,103 @@ std::vector<Event> Davis::integrate_frame_gaps() {
     return video_.integrate_sparse(steps);
 }
 
+Davis::~Davis() {
+    if (dv_) adder_davis_destroy(dv_);
+}
+
+Davis &Davis::chain_on_device(bool on) {
+    if (dv_ || have_start_ || have_last_after_)
+        throw SourceError(SourceError::BadParams, "chain_on_device must be set before the first packet");
+    chain_on_device_ = on;
+    return *this;
+}
+
+void Davis::take_packet_times(const DavisPacket &pk) {
+    time_change_ = (double)(pk.img_start_ts - (have_start_ ? start_of_frame_timestamp_ : 0));
+    num_dvs_events_ = pk.events_before.size() + pk.events_after.size();
+    start_of_frame_timestamp_ = pk.img_start_ts;
+    end_of_frame_timestamp_ = pk.img_end_ts;
+    have_start_ = have_end_ = true;
+    if (mode_ == TranscoderMode::RawDvs) end_of_frame_timestamp_ = pk.img_start_ts + 1;
+    ref_time_divisor_ = (double)(pk.img_end_ts - pk.img_start_ts) / (double)video_.get_ref_time();
+}
+
+// consume() with the chain on the device: one adder_davis_push_host per packet, adder_davis_finish_host at the end
+std::vector<std::vector<Event>> Davis::consume_on_device() {
+    const size_t W = video_.plane().w(), H = video_.plane().h(), n = W * H;
+    std::vector<std::vector<Event>> ret;
+    auto fail = [&](const char *what) {
+        throw SourceError(SourceError::BadParams, std::string(what) + ": " + adder_davis_last_error(dv_));
+    };
+    auto take = [&](const std::vector<Event> &ev) {  // what the host path's log() and Video::integrate_sparse do
+        ingested_.insert(ingested_.end(), ev.begin(), ev.end());
+        video_.ingest_events(ev.data(), ev.size());
+    };
+    if (have_cached_) {
+        have_cached_ = false;
+        if (!dv_) {
+            if (video_.get_pixel_time_mode() != TimeMode::AbsoluteT)
+                throw SourceError(SourceError::BadParams, "Davis::chain_on_device: AbsoluteT only");
+            AdderDavisParams p{};
+            p.abi_version = ADDER_DAVIS_ABI_VERSION;
+            p.width = (uint16_t)W;
+            p.height = (uint16_t)H;
+            p.mode = mode_ == TranscoderMode::Framed ? ADDER_DAVIS_FRAMED
+                                                     : mode_ == TranscoderMode::RawDavis ? ADDER_DAVIS_RAW_DAVIS : ADDER_DAVIS_RAW_DVS;
+            p.tps = video_.get_tps();
+            p.ref_time = video_.get_ref_time();
+            p.delta_t_max = video_.get_delta_t_max();
+            p.crf = crf_ ? (int32_t)*crf_ : ADDER_DAVIS_NO_CRF;
+            p.device_id = video_.get_device_id() < 0 ? 0 : video_.get_device_id();
+            if (adder_davis_create(&p, &dv_) != ADDER_OK) {
+                dv_ = nullptr;
+                fail("adder_davis_create");
+            }
+        }
+        const uint64_t eps = adder_davis_events_per_step(dv_);
+        if (cached_end_) {
+            std::vector<Event> ev(n * eps);
+            uint64_t got = 0;
+            if (adder_davis_finish_host(dv_, reinterpret_cast<AdderEvent *>(ev.data()), ev.size(), &got) != ADDER_OK)
+                fail("adder_davis_finish_host");
+            ev.resize(got);
+            take(ev);
+            throw SourceError(SourceError::NoData, "End of input");
+        }
+        DavisPacket pk = std::move(cached_);
+        if (pk.frame.size() != n) throw SourceError(SourceError::BadParams, "Davis: a frame of the wrong size");
+        if (pk.has_events) take_packet_times(pk);
+        auto convert = [](const std::vector<DavisDvsEvent> &src) {
+            std::vector<AdderDavisEvent> dst(src.size());
+            for (size_t i = 0; i < src.size(); ++i) dst[i] = AdderDavisEvent{src[i].t, src[i].x, src[i].y, (uint8_t)src[i].on, {0, 0, 0}};
+            return dst;
+        };
+        const std::vector<AdderDavisEvent> before = convert(pk.events_before), after = convert(pk.events_after);
+        AdderDavisMeta meta{};
+        meta.c = pk.c;
+        meta.img_start_ts = pk.img_start_ts;
+        meta.img_end_ts = pk.img_end_ts;
+        meta.has_events = pk.has_events ? 1u : 0u;
+        std::vector<Event> ev(adder_davis_push_capacity(dv_, before.size()));
+        uint64_t got = 0, bad = 0;
+        if (adder_davis_push_host(dv_, pk.frame.data(), &meta, before.data(), before.size(), after.data(), after.size(),
+                                  reinterpret_cast<AdderEvent *>(ev.data()), ev.size(), &got, &bad) != ADDER_OK)
+            fail("adder_davis_push_host");
+        ev.resize(got);
+        take(ev);
+        // consume() returns the frame's events alone, one vector per row chunk
+        const size_t chunk_rows = video_.get_chunk_rows();
+        ret.assign((H + chunk_rows - 1) / chunk_rows, {});
+        for (size_t i = got - adder_davis_last_frame_events(dv_); i < got; ++i) ret[ev[i].y / chunk_rows].push_back(ev[i]);
+    }
+    cached_ = DavisPacket();
+    cached_end_ = !next_packet_(cached_);
+    have_cached_ = true;
+    return ret;
+}
+
 std::vector<std::vector<Event>> Davis::consume() {
+    if (chain_on_device_) return consume_on_device();
     const bool with_events = mode_ != TranscoderMode::Framed;
     const size_t W = video_.plane().w(), H = video_.plane().h(), n = W * H;
     std::vector<std::vector<Event>> ret;

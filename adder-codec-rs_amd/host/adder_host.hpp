@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/adder_davis.h"
 #include "../../include/adder_framer.h"
 #include "../../include/adder_hip.h"
 
@@ -247,6 +248,10 @@ class Video {
     // what the event-camera sources do with their pixels: one `integrate_for_px(px, &mut 0, frame_val, intensity,
     // time, &mut events, ..)` per step, in order (prophesee.rs:196-254); the events are also pushed through the encoder
     std::vector<Event> integrate_sparse(const std::vector<AdderSparseStep> &steps);
+    // events a source integrated outside this Video's context (Davis::chain_on_device): through the encoder alone
+    void ingest_events(const Event *events, size_t n);
+    TimeMode get_pixel_time_mode() const { return px_time_mode_; }
+    int get_device_id() const { return device_id_; }
 
   private:
     std::vector<std::vector<Event>> integrate_one(const uint8_t *frame, bool rgb, float time_spanned);
@@ -400,10 +405,15 @@ class Davis : public Source {
     // reference indexes four event chunks by y / (h / 4), :254-258).
     Davis(uint16_t width, uint16_t height, TranscoderMode mode, std::function<bool(DavisPacket &)> next_packet,
           int device_id = -1);
+    ~Davis() override;
+    // Off (default): the per-pixel chain runs in consume() on the host and the steps are uploaded.  On: consume() hands
+    // each packet to adder_davis_push_host / _finish_host (include/adder_davis.h) on a context with this source's
+    // parameters as they stand at the first packet (AbsoluteT only); the Video's own context is then never made.
+    Davis &chain_on_device(bool on);
     // :601-897 -- the frame's events; the first call only fetches (the reference keeps one packet cached); throws
     // SourceError::NoData after the last pixel flush at the end of the input
     std::vector<std::vector<Event>> consume() override;
-    void crf(uint8_t crf) override { video_.update_crf(crf); }
+    void crf(uint8_t crf) override { video_.update_crf(crf); crf_ = crf; }
     Video &get_video_mut() override { return video_; }
     const Video &get_video_ref() const override { return video_; }
     const Frame *get_input() const override { return nullptr; }
@@ -416,6 +426,11 @@ class Davis : public Source {
     std::vector<Event> integrate_dvs_events(const std::vector<DavisDvsEvent> &ev, int64_t frame_timestamp, bool check2_after,
                                             bool has_ts2, int64_t frame_timestamp_2);  // :233-466
     std::vector<Event> integrate_frame_gaps();                                          // :468-598
+    std::vector<std::vector<Event>> consume_on_device();
+    void take_packet_times(const DavisPacket &pk);  // :668-699, the fields get_running_input_bitrate reads
+    bool chain_on_device_ = false;
+    AdderDavis *dv_ = nullptr;
+    std::optional<uint8_t> crf_;
     std::function<bool(DavisPacket &)> next_packet_;
     Video video_;
     TranscoderMode mode_;

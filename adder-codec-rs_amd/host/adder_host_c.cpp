@@ -231,9 +231,10 @@ long long adder_host_prophesee(const uint8_t *dvs, size_t n, uint16_t width, uin
 // frames = [P][h * w] f64; meta = [P] records {c f64, img_start_ts i64, img_end_ts i64, n_before u32, n_after u32};
 // dvs = the packets' before-events then after-events, one packet after the other, as {t i64, x u16, y u16, on u8, pad[3]}.
 // out receives every event the source ingests, in order; returned = their number; *n_returned = events consume() returned.
-long long adder_host_davis(const double *frames, const uint8_t *meta, const uint8_t *dvs, uint32_t packets, uint16_t width,
+static long long davis_run(const double *frames, const uint8_t *meta, const uint8_t *dvs, uint32_t packets, uint16_t width,
                            uint16_t height, int mode, uint32_t tps, uint32_t ref_time, uint32_t delta_t_max, int time_mode,
-                           int crf /* <0: none */, AdderEvent *out, size_t cap, unsigned long long *n_returned) {
+                           int crf /* <0: none */, AdderEvent *out, size_t cap, unsigned long long *n_returned,
+                           bool chain_on_device) {
     try {
         uint32_t pos = 0;
         size_t dvs_pos = 0;
@@ -268,6 +269,7 @@ long long adder_host_davis(const double *frames, const uint8_t *meta, const uint
                      next);
         source.get_video_mut().time_parameters(tps, ref_time, delta_t_max, time_mode == 1 ? TimeMode::AbsoluteT : TimeMode::DeltaT);
         if (crf >= 0) source.crf((uint8_t)crf);
+        source.chain_on_device(chain_on_device);
         unsigned long long returned = 0;
         for (;;) {
             try {
@@ -285,6 +287,22 @@ long long adder_host_davis(const double *frames, const uint8_t *meta, const uint
         g_err = e.what();
         return -1;
     }
+}
+
+long long adder_host_davis(const double *frames, const uint8_t *meta, const uint8_t *dvs, uint32_t packets, uint16_t width,
+                           uint16_t height, int mode, uint32_t tps, uint32_t ref_time, uint32_t delta_t_max, int time_mode,
+                           int crf /* <0: none */, AdderEvent *out, size_t cap, unsigned long long *n_returned) {
+    return davis_run(frames, meta, dvs, packets, width, height, mode, tps, ref_time, delta_t_max, time_mode, crf, out, cap,
+                     n_returned, false);
+}
+
+// The same with Davis::chain_on_device(true): every packet through adder_davis_push_host (include/adder_davis.h).
+long long adder_host_davis_device(const double *frames, const uint8_t *meta, const uint8_t *dvs, uint32_t packets,
+                                  uint16_t width, uint16_t height, int mode, uint32_t tps, uint32_t ref_time,
+                                  uint32_t delta_t_max, int time_mode, int crf /* <0: none */, AdderEvent *out, size_t cap,
+                                  unsigned long long *n_returned) {
+    return davis_run(frames, meta, dvs, packets, width, height, mode, tps, ref_time, delta_t_max, time_mode, crf, out, cap,
+                     n_returned, true);
 }
 
 long long adder_host_transcode_raw(const uint8_t *frames, uint32_t num_frames, uint32_t width, uint32_t height,
