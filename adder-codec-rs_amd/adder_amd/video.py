@@ -238,6 +238,19 @@ class HipVideo:
         N.check(self.h, rc)
         return out[: n.value].copy()
 
+    def integrate_sparse_device(self, d_steps, n, d_out, out_cap, stream=None):
+        """The same with the steps and the events in device memory (adder_hip_integrate_sparse_device): d_steps holds n
+        AdderSparseSteps, d_out has room for out_cap AdderEvents; tensors or raw device pointers.  Runs on `stream` (a raw
+        hipStream_t; None = the context's own), waits for it, and returns the number of events."""
+        p_steps = d_steps.data_ptr() if hasattr(d_steps, "data_ptr") else d_steps
+        p_out = d_out.data_ptr() if hasattr(d_out, "data_ptr") else d_out
+        got = C.c_size_t(0)
+        rc = self.L.adder_hip_integrate_sparse_device(self.h, p_steps, n, p_out, out_cap, C.byref(got),
+                                                      C.c_void_p(stream) if stream else None)
+        self.last_required = got.value
+        N.check(self.h, rc)
+        return got.value
+
     # ---- per-frame ring: submit returns once the work is queued, collect hands back the oldest frame --------
     def frames_configure(self, slots=0, events_per_slot=0):
         N.check(self.h, self.L.adder_hip_frames_configure(self.h, slots, events_per_slot))

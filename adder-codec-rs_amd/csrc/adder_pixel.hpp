@@ -1967,6 +1967,11 @@ constexpr uint32_t kSparseNoSide = 1u, kSparseIntegrateOnly = 2u, kSparseTestOnl
 template <bool ABS_T, class Acc, class Emit>
 ADDER_HD bool cont_step(APx &s, Acc &acc, uint32_t v, float intensity, float time, const StepConsts &sc,
                         uint32_t max_nodes, Emit &emit, uint32_t kind = 0u) {
+    // A step that needed more than max_nodes (below) leaves a fired node without a child.  A flush that integrates
+    // nothing (kSparseTestOnly, kSparseFlush) can make that node the root of a one-node arena, and the next
+    // pop_top_event then shifts the arena down to length 0.  The call has failed by then; the pixel is not stepped
+    // again, so that no node index is ever formed from `length - 1` of an empty arena.
+    if (s.length == 0u) return false;
     bool ok = true;
     const bool flush_only = (kind & kSparseFlush) != 0u;
     // ---- pop_best_events (:213-287) + set_d_for_continuous (:289-312) ----
@@ -2082,9 +2087,13 @@ ADDER_HD bool cont_step(APx &s, Acc &acc, uint32_t v, float intensity, float tim
                 root.has_best = true;
                 root.bd = root.integ < 1.0f ? kDZero : get_d(root.integ);
                 root.bdt = root.dt;
-                if (max_nodes < 2u) ok = false;
-                acc.store(1, anode_new(intensity));
-                s.length = 2u;
+                if (max_nodes < 2u) {  // no room for the fresh node: the step fails and the root stays where it is
+                    ok = false;
+                    shifted = false;
+                } else {
+                    acc.store(1, anode_new(intensity));
+                    s.length = 2u;
+                }
                 ed = root.bd;
                 edt = root.bdt;
             }

@@ -153,7 +153,9 @@ __global__ __launch_bounds__(256) void adder_sparse_emit_kernel(const SparseStep
         AdderEventPod ev;
         ev.x = st.x;
         ev.y = st.y;
-        ev.c = st.c;
+        // the PIXEL's coordinate, as every event of the reference carries it: no channel on a one-channel plane, and
+        // channel 0 for a step that names none on a plane with several (sparse_unit)
+        ev.c = a.channels == 1u ? 0xffu : (st.c == 0xffu ? 0u : st.c);
         ev.d = (uint8_t)r.y;
         ev.pad = 0;
         ev.t = r.x;

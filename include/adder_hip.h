@@ -231,7 +231,9 @@ int adder_hip_frame_collect_wire(AdderHipCtx *ctx, const uint8_t **bytes, size_t
 #define ADDER_SPARSE_FLUSH 8u
 typedef struct AdderSparseStep {
     uint16_t x, y;      /* plane coordinates */
-    uint8_t c;          /* channel, ADDER_C_NONE on a 1-channel plane */
+    uint8_t c;          /* channel, ADDER_C_NONE on a 1-channel plane (ADDER_C_NONE on a plane with several channels
+                         * names channel 0, and 0 the one channel of a 1-channel plane: the events carry the PIXEL's
+                         * coordinate either way, as the reference's do) */
     uint8_t frame_val;  /* compared with the pixel's base_val +- c_thresh (video.rs:1336-1340; the sources' `&mut 0` is an
                          * out parameter that integrate_for_px overwrites with px.base_val) */
     uint16_t pad;       /* flags: ADDER_SPARSE_NO_SIDE, else 0 */

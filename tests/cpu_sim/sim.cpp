@@ -58,6 +58,9 @@ struct Sim {
     // sparse steps (event-camera sources): running_t per unit as well, from the first sparse call on
     int sparse;
     std::vector<float> rt_px;
+    // ContAcc's bounds check: the first node index >= max_depth + 1 a Continuous step asked for (the access is not made)
+    int node_oob;
+    uint32_t node_oob_index;
 };
 
 struct DeepAcc {
@@ -82,7 +85,15 @@ struct DeepAcc {
 struct ContAcc {
     Sim *s;
     size_t u;
+    // the node planes hold max_depth + 1 nodes per unit: anything else is recorded, not touched (kSimNodeOutOfRange)
+    bool in_range(uint32_t k) const {
+        if (k < s->max_depth + 1u) return true;
+        if (!s->node_oob) s->node_oob_index = k;
+        s->node_oob = 1;
+        return false;
+    }
     ANode load(uint32_t k) const {
+        if (!in_range(k)) return anode_new(0.0f);
         const size_t i = (size_t)k * s->N + u;
         ANode n;
         n.integ = s->c_integ[i];
@@ -92,6 +103,7 @@ struct ContAcc {
         return n;
     }
     void store(uint32_t k, const ANode &n) const {
+        if (!in_range(k)) return;
         const size_t i = (size_t)k * s->N + u;
         s->c_integ[i] = n.integ;
         s->c_dt[i] = n.dt;
@@ -99,6 +111,8 @@ struct ContAcc {
         s->c_meta[i] = anode_meta(n);
     }
 };
+
+constexpr int kSimNodeOutOfRange = -11;  // a Continuous step asked ContAcc for a node outside the unit's arena
 
 struct Emitter {
     SimEvent *out;
@@ -155,6 +169,8 @@ Sim *sim_new(uint32_t W, uint32_t H, uint32_t C, uint32_t row_begin, int time_mo
     s->fset.assign((size_t)W * H, 0);
     s->new_features = 0;
     s->sparse = 0;
+    s->node_oob = 0;
+    s->node_oob_index = 0;
     return s;
 }
 void sim_free(Sim *s) { delete s; }
@@ -178,7 +194,13 @@ void sim_reset_c_thresh(Sim *s, uint8_t baseline) {
     s->c_thresh = baseline;
     s->c_counter = 0;
     s->perpx = 0;
+    if (s->sparse) {  // sparse contexts keep the pair per unit (adder_hip_reset_c_thresh): every unit gets (baseline, 0)
+        s->cth_px.assign(s->N, baseline);
+        s->cctr_px.assign(s->N, 0);
+    }
 }
+void sim_running_plane(const Sim *s, uint8_t *out) { memcpy(out, s->running.data(), s->N); }
+uint32_t sim_node_oob_index(const Sim *s) { return s->node_oob_index; }
 void sim_update_detect_features(Sim *s, int detect, int adjust, uint32_t baseline, uint32_t radius, uint32_t chunk_rows) {
     s->feat_detect = detect; s->feat_adjust = adjust; s->baseline = baseline; s->radius = radius;
     s->chunk_rows = chunk_rows ? chunk_rows : 1;
@@ -219,6 +241,7 @@ struct SimSparseStep {
 };
 int sim_integrate_sparse(Sim *s, const SimSparseStep *steps, size_t n, SimEvent *out, size_t cap, size_t *n_out) {
     if (!s->continuous) return -1;
+    s->node_oob = 0;
     if (!s->sparse) {
         s->cth_px.assign(s->N, s->c_thresh);
         s->cctr_px.assign(s->N, s->c_counter);
@@ -239,7 +262,7 @@ int sim_integrate_sparse(Sim *s, const SimSparseStep *steps, size_t n, SimEvent 
         const uint32_t c = steps[i].c == 0xFF ? 0u : steps[i].c;
         if (steps[i].x >= s->W || steps[i].y < s->row_begin || steps[i].y - s->row_begin >= s->H || c >= s->C) return -1;
         const size_t u = ((size_t)(steps[i].y - s->row_begin) * s->W + steps[i].x) * s->C + c;
-        em.x = steps[i].x; em.y = steps[i].y; em.c = steps[i].c;
+        em.x = steps[i].x; em.y = steps[i].y; em.c = s->C == 1 ? 0xFF : (uint8_t)c;  // (the pixel's own coordinate)
         APx p = apx_unpack(s->c_hdr[u], s->lastf[u]);
         sc.time_spanned = steps[i].time;
         sc.running_t = s->rt_px[u];
@@ -256,9 +279,14 @@ int sim_integrate_sparse(Sim *s, const SimSparseStep *steps, size_t n, SimEvent 
             s->rt_px[u] += steps[i].time;
             c_thresh_advance(s->cth_px[u], s->cctr_px[u], (uint8_t)s->c_max, (uint8_t)s->velocity, steps[i].time, s->ref_time);
         }
+        if (!(kind & kSparseNoSide)) {  // the side plane, as adder_sparse_run_kernel samples it (Intensity view)
+            const ANode r = acc.load(0);
+            if (r.has_best) s->running[u] = (uint8_t)frame_value_u8(r.bd, f32_as_u32(r.bdt), (double)s->ref_time);
+        }
     }
     *n_out = em.pos;
     if (em.pos > cap && rc == 0) rc = -4;
+    if (s->node_oob) rc = kSimNodeOutOfRange;
     return rc;
 }
 
@@ -826,6 +854,7 @@ int sim_integrate(Sim *s, const uint8_t *frame, float time_spanned, SimEvent *ou
     // delta_t_max <= time_spanned and no generic batch has run since the last reset
     // feature path (adder_hip_batch.cpp prepare_per_unit_c_thresh): one pair per unit from the first frame that can
     // make them differ
+    s->node_oob = 0;
     const bool needs_perpx = s->roi_on || (s->feat_detect && s->feat_adjust && s->radius > 0);
     if (needs_perpx && !s->perpx) {
         s->cth_px.assign(s->N, s->c_thresh);
@@ -861,6 +890,8 @@ int sim_integrate(Sim *s, const uint8_t *frame, float time_spanned, SimEvent *ou
                     s->c_hdr[u] = apx_hdr(p);
                     s->lastf[u] = p.lastf;
                     if (p.length > s->max_m) s->max_m = p.length;
+                    const ANode r = acc.load(0);  // the side plane, as adder_cont_kernel writes it
+                    if (r.has_best) s->running[u] = (uint8_t)frame_value_u8(r.bd, f32_as_u32(r.bdt), (double)s->ref_time);
                     continue;
                 }
                 if (s->perpx) {
@@ -965,6 +996,7 @@ int sim_integrate(Sim *s, const uint8_t *frame, float time_spanned, SimEvent *ou
     c_thresh_advance(s->c_thresh, s->c_counter, (uint8_t)s->c_max, (uint8_t)s->velocity, time_spanned, s->ref_time);
     *n_out = em.pos;
     if (em.pos > cap && rc == 0) rc = -4;
+    if (s->node_oob) rc = kSimNodeOutOfRange;
     return rc;
 }
 }

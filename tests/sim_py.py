@@ -15,6 +15,8 @@ EVENT_DTYPE = np.dtype(
     [("x", "<u2"), ("y", "<u2"), ("c", "u1"), ("d", "u1"), ("pad", "<u2"), ("t", "<u4")]
 )
 
+NODE_OUT_OF_RANGE = -11  # sim.cpp kSimNodeOutOfRange: a Continuous step asked for a node outside its unit's arena
+
 _lib = None
 
 
@@ -158,6 +160,20 @@ class Sim:
                                                 C.POINTER(C.c_size_t)]
         rc = self.L.sim_integrate_sparse(self.h, steps.ctypes.data, len(steps), out.ctypes.data, cap, C.byref(n))
         return rc, out[: n.value].copy()
+
+    def running_plane(self):
+        """The running-intensities side plane (Intensity view), flat [units]."""
+        out = np.zeros(self.n, np.uint8)
+        self.L.sim_running_plane.argtypes = [C.c_void_p, C.c_void_p]
+        self.L.sim_running_plane(self.h, out.ctypes.data)
+        return out
+
+    @property
+    def node_oob_index(self):
+        """The node index behind the last NODE_OUT_OF_RANGE (the sim's ContAcc records it and skips the access)."""
+        self.L.sim_node_oob_index.restype = C.c_uint32
+        self.L.sim_node_oob_index.argtypes = [C.c_void_p]
+        return int(self.L.sim_node_oob_index(self.h))
 
     def update_detect_features(self, detect, adjust, baseline, radius, chunk_rows=1):
         self.L.sim_update_detect_features(self.h, int(detect), int(adjust), baseline, radius, chunk_rows)
