@@ -326,6 +326,64 @@ class Handle:
             pass
 
 
+def device_buffer(t, dev, what):
+    if not (t.is_cuda and t.device == dev and t.is_contiguous()):
+        raise ValueError(f"{what}: a contiguous CUDA tensor on {dev} is needed (got {t.device}, "
+                         f"contiguous={t.is_contiguous()})")
+
+
+class SourceHandle(Handle):
+    """What the camera sources (HipProphesee, HipDavis) do alike around a C-ABI whose functions are PREFIX_reset,
+    PREFIX_last_error, PREFIX_finish_host, ...: a class sets PREFIX and DESTROY and, at create, self.L, self.h,
+    self.width, self.height, self.device_id, self.events_per_step and self.bad_index."""
+    PREFIX = None
+    NO_BAD = (1 << 64) - 1  # ADDER_PROPHESEE_NO_BAD_RECORD, ADDER_DAVIS_NO_BAD_EVENT
+
+    def _fn(self, name):
+        return getattr(self.L, f"{self.PREFIX}_{name}")
+
+    def _error(self, rc):
+        return AdderHipError(rc, (self._fn("last_error")(self.h) or b"").decode())
+
+    def _check(self, rc):
+        if rc != OK:
+            raise self._error(rc)
+
+    def _done(self, rc, bad, n_out):
+        """After a push: .bad_index; a refusal raises with .index and .needed (a room that succeeds)."""
+        if bad.value != self.NO_BAD:
+            self.bad_index = bad.value
+        if rc != OK:
+            err = self._error(rc)
+            err.index, err.needed = self.bad_index, n_out.value
+            raise err
+
+    def _device_out(self, dev, out_cap, d_out):
+        """The device push's output -> (uint8 view of d_out, or of a new tensor of out_cap events; out_cap)."""
+        import torch
+        if d_out is None:
+            d_out = torch.empty(max(out_cap, 1) * 12, dtype=torch.uint8, device=dev)
+        else:  # the library writes at most out_cap events: never more than the tensor holds
+            device_buffer(d_out, dev, "d_out")
+            out_cap = min(out_cap, d_out.numel() * d_out.element_size() // 12)
+        return d_out.reshape(-1).view(torch.uint8), out_cap
+
+    def reset(self):
+        self._check(self._fn("reset")(self.h))
+
+    def finish(self):
+        cap = self.width * self.height * self.events_per_step
+        out = np.zeros(cap, EVENT_DTYPE)
+        n = C.c_uint64(0)
+        self._check(self._fn("finish_host")(self.h, out.ctypes.data, cap, C.byref(n)))
+        return out[: n.value].copy()
+
+    def running_intensities(self):
+        out = np.zeros((self.height, self.width), np.uint8)
+        self._check(self._fn("running_intensities")(self.h, out.ctypes.data))
+        return out
+
+
 def check_framer(fr, rc):
     if rc != OK:
         msg = load().adder_framer_last_error(fr)

@@ -126,17 +126,11 @@ def frame_host(width, height, mode, frame, start, end, last_ts, last_ln):
     return img.reshape(shape), (steps if mode != FRAMED else steps[:0]), ts.reshape(shape), ln.reshape(shape)
 
 
-def _device_buffer(t, dev, what):
-    if not (t.is_cuda and t.device == dev and t.is_contiguous()):
-        raise ValueError(f"{what}: a contiguous CUDA tensor on {dev} is needed (got {t.device}, "
-                         f"contiguous={t.is_contiguous()})")
-
-
-class HipDavis(N.Handle):
+class HipDavis(N.SourceHandle):
     """Davis::new(..)[.crf(c)] with time_parameters(tps, ref_time, delta_t_max, AbsoluteT) on one device: push() one
     packet after the other, finish() at the end of input.  After a refused push, .bad_index is the index of the event
     outside the plane (`before` first, `after` following; else None)."""
-    DESTROY = "adder_davis_destroy"
+    PREFIX, DESTROY = "adder_davis", "adder_davis_destroy"
 
     def __init__(self, width, height, mode, tps, ref_time, delta_t_max, crf=None, device_id=0):
         self.L = load()
@@ -150,13 +144,6 @@ class HipDavis(N.Handle):
         self.width, self.height, self.mode, self.device_id = width, height, mode, device_id
         self.events_per_step = self.L.adder_davis_events_per_step(h)
         self.bad_index = None
-
-    def _check(self, rc):
-        if rc != N.OK:
-            raise N.AdderHipError(rc, (self.L.adder_davis_last_error(self.h) or b"").decode())
-
-    def reset(self):
-        self._check(self.L.adder_davis_reset(self.h))
 
     def push_capacity(self, n_before):
         return self.L.adder_davis_push_capacity(self.h, n_before)
@@ -188,45 +175,25 @@ class HipDavis(N.Handle):
             return out[: n_out.value].copy()
         import torch
         dev = torch.device(f"cuda:{self.device_id}")
-        _device_buffer(frame, dev, "frame")
+        N.device_buffer(frame, dev, "frame")
         if frame.dtype != torch.float64 or frame.numel() != self.width * self.height:
             raise ValueError("frame: float64, width * height values")
 
         def lst(t, what):
             if t is None or (not hasattr(t, "is_cuda") and len(t) == 0):
                 return None, 0
-            _device_buffer(t, dev, what)
+            N.device_buffer(t, dev, what)
             n = t.numel() * t.element_size() // 16
             return (t.data_ptr() if n else None), n
         pb, nb = lst(before, "before")
         pa, na = lst(after, "after")
         if out_cap is None:
             out_cap = self.push_capacity(nb)
-        if d_out is None:
-            d_out = torch.empty(max(out_cap, 1) * 12, dtype=torch.uint8, device=dev)
-        else:  # the library writes at most out_cap events: never more than the tensor holds
-            _device_buffer(d_out, dev, "d_out")
-            out_cap = min(out_cap, d_out.numel() * d_out.element_size() // 12)
-        d_out = d_out.reshape(-1).view(torch.uint8)
+        d_out, out_cap = self._device_out(dev, out_cap, d_out)
         rc = self.L.adder_davis_push_device(self.h, frame.data_ptr(), C.byref(meta), pb, nb, pa, na, d_out.data_ptr(),
                                             out_cap, C.byref(n_out), C.byref(bad), C.c_void_p(stream) if stream else None)
         self._done(rc, bad, n_out)
         return d_out[: n_out.value * 12]
-
-    def _done(self, rc, bad, n_out):
-        if bad.value != NO_BAD_EVENT:
-            self.bad_index = bad.value
-        if rc != N.OK:
-            err = N.AdderHipError(rc, (self.L.adder_davis_last_error(self.h) or b"").decode())
-            err.index, err.needed = self.bad_index, n_out.value
-            raise err
-
-    def finish(self):
-        cap = self.width * self.height * self.events_per_step
-        out = np.zeros(max(cap, 1), N.EVENT_DTYPE)
-        n = C.c_uint64(0)
-        self._check(self.L.adder_davis_finish_host(self.h, out.ctypes.data, cap, C.byref(n)))
-        return out[: n.value].copy()
 
     def pixel_state(self):
         """The camera state the last accepted push left -> (last ts, last ln): (H, W) int64 and float64 planes."""
@@ -234,11 +201,6 @@ class HipDavis(N.Handle):
         ln = np.zeros((self.height, self.width), np.float64)
         self._check(self.L.adder_davis_pixel_state(self.h, ts.ctypes.data, ln.ctypes.data))
         return ts, ln
-
-    def running_intensities(self):
-        out = np.zeros((self.height, self.width), np.uint8)
-        self._check(self.L.adder_davis_running_intensities(self.h, out.ctypes.data))
-        return out
 
 
 def davis_to_adder(packets, width, height, mode, *, tps, ref_time, delta_t_max, crf=None, device_id=0, sink=None):

@@ -132,17 +132,11 @@ def records(t, x, y, p):
     return r
 
 
-def _device_buffer(t, dev, what):
-    if not (t.is_cuda and t.device == dev and t.is_contiguous()):
-        raise ValueError(f"{what}: a contiguous CUDA tensor on {dev} is needed (got {t.device}, "
-                         f"contiguous={t.is_contiguous()})")
-
-
-class HipProphesee(N.Handle):
+class HipProphesee(N.SourceHandle):
     """Prophesee::new(ref_time, ..)[.crf(c)] on one device: start() runs the two start-up frames, push() any split
     of the record stream, finish() the end of input.  After a refused push, .bad_index is the stream index of the
     record outside the plane (else None)."""
-    DESTROY = "adder_prophesee_destroy"
+    PREFIX, DESTROY = "adder_prophesee", "adder_prophesee_destroy"
 
     def __init__(self, width, height, ref_time=1, crf=NO_CRF, device_id=0):
         self.L = load()
@@ -156,13 +150,6 @@ class HipProphesee(N.Handle):
         self.width, self.height, self.ref_time, self.device_id = width, height, ref_time, device_id
         self.events_per_step = self.L.adder_prophesee_events_per_step(h)
         self.bad_index = None
-
-    def _check(self, rc):
-        if rc != N.OK:
-            raise N.AdderHipError(rc, (self.L.adder_prophesee_last_error(self.h) or b"").decode())
-
-    def reset(self):
-        self._check(self.L.adder_prophesee_reset(self.h))
 
     def state(self):
         rt, gs, op, pushed = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
@@ -198,35 +185,15 @@ class HipProphesee(N.Handle):
             return out[: n_out.value].copy()
         import torch
         dev = torch.device(f"cuda:{self.device_id}")
-        _device_buffer(recs, dev, "records")
+        N.device_buffer(recs, dev, "records")
         n = recs.numel() * recs.element_size() // 8
         if out_cap is None:
             out_cap = 2 * (n + self.state()["open_records"]) * self.events_per_step
-        if d_out is None:
-            d_out = torch.empty(max(out_cap, 1) * 12, dtype=torch.uint8, device=dev)
-        else:  # the library writes at most out_cap events: never more than the tensor holds
-            _device_buffer(d_out, dev, "d_out")
-            out_cap = min(out_cap, d_out.numel() * d_out.element_size() // 12)
-        d_out = d_out.reshape(-1).view(torch.uint8)
+        d_out, out_cap = self._device_out(dev, out_cap, d_out)
         rc = self.L.adder_prophesee_push_device(self.h, recs.data_ptr() if n else None, n, d_out.data_ptr(), out_cap,
                                                 C.byref(n_out), C.byref(bad), C.c_void_p(stream) if stream else None)
         self._done(rc, bad, n_out)
         return d_out[: n_out.value * 12]
-
-    def _done(self, rc, bad, n_out):
-        if bad.value != NO_BAD_RECORD:
-            self.bad_index = bad.value
-        if rc != N.OK:
-            err = N.AdderHipError(rc, (self.L.adder_prophesee_last_error(self.h) or b"").decode())
-            err.index, err.needed = self.bad_index, n_out.value
-            raise err
-
-    def finish(self):
-        cap = self.width * self.height * self.events_per_step
-        out = np.zeros(cap, N.EVENT_DTYPE)
-        n = C.c_uint64(0)
-        self._check(self.L.adder_prophesee_finish_host(self.h, out.ctypes.data, cap, C.byref(n)))
-        return out[: n.value].copy()
 
     def pixel_state(self):
         """The camera state the last accepted push left -> (last t, last ln): (H, W) uint32 and float64 planes."""
@@ -234,11 +201,6 @@ class HipProphesee(N.Handle):
         ln = np.zeros((self.height, self.width), np.float64)
         self._check(self.L.adder_prophesee_pixel_state(self.h, t.ctypes.data, ln.ctypes.data))
         return t, ln
-
-    def running_intensities(self):
-        out = np.zeros((self.height, self.width), np.uint8)
-        self._check(self.L.adder_prophesee_running_intensities(self.h, out.ctypes.data))
-        return out
 
 
 def stream_meta(width, height, ref_time, compressed):

@@ -11,6 +11,7 @@
 #include <string>
 
 #include "../../include/adder_hip.h"  // ADDER_OK, ADDER_E_*
+#include "adder_sort_util.hpp"        // the rules without HIP: key_bits_for, scratch_capacity, kCrf
 
 namespace adder {
 

@@ -14,10 +14,10 @@
 //   4. an exclusive scan of the counts in step order places the steps; a lane per event copies them (coalesced);
 //   5. gaps: a lane per pixel on the work planes, 0 / 1 counts, scan, compaction behind the events' steps;
 //   6. frame: a lane per pixel -- the frame check, image_8u, the pixel's step behind the gaps', last ln, last ts.
+// The sorts, the scans and the compaction of step 4 are adder_chain.hip's, shared with adder_prophesee.hip.
 // Everything works on a copy of the state planes: the host commits by swapping the planes once it has read the
 // bad-event and bad-frame words, so a refused push changes nothing.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 #include "adder_davis_kernels.h"
@@ -141,22 +141,6 @@ __global__ __launch_bounds__(256) void davis_walk_kernel(DavisArgs a, DavisPacke
     work.ln[u] = px.ln;
 }
 
-__global__ void davis_total_kernel(const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ offs, uint64_t n,
-                                   DavisScalars *sc) {
-    sc->ev_steps = (unsigned long long)offs[n - 1] + cnt[n - 1];
-}
-
-__global__ __launch_bounds__(256) void davis_scatter_kernel(uint64_t n, const uint32_t *__restrict__ cnt,
-                                                            const uint32_t *__restrict__ offs,
-                                                            const AdderSparseStep *__restrict__ stage,
-                                                            AdderSparseStep *__restrict__ steps) {
-    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (r >= n) return;
-    const uint32_t c = cnt[r];
-    const uint64_t o = offs[r];
-    for (uint32_t q = 0; q < c; ++q) steps[o + q] = stage[2u * r + q];
-}
-
 __global__ __launch_bounds__(256) void davis_gaps_kernel(DavisArgs a, DavisPacket pk, DavisPlanes work,
                                                          uint32_t *__restrict__ gcnt, AdderSparseStep *__restrict__ gstage) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
@@ -210,69 +194,36 @@ __global__ __launch_bounds__(256) void davis_flush_kernel(DavisArgs a, AdderSpar
     steps[p] = davis_step(p % a.width, p / a.width, 0u, ADDER_SPARSE_NO_SIDE | ADDER_SPARSE_FLUSH, 0.0f, 0.0f);
 }
 
-static uint32_t grid_of(uint64_t n) { return (uint32_t)((n + 255u) / 256u); }
-
-size_t davis_temp_bytes(uint64_t n_events, uint32_t units) {
-    size_t a = 0, b = 0, c = 0;
-    if (n_events) {
-        hipcub::DoubleBuffer<uint32_t> k(nullptr, nullptr), v(nullptr, nullptr);
-        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, k, v, (int)n_events);
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n_events);
-    }
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, c, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)units);
-    if (b > a) a = b;
-    if (c > a) a = c;
-    return a + 256;
-}
-
-// sorts (s.keys0, s.idx0) by the low `bits` bits; the result ends in keys0 / idx0
-static hipError_t sort_pairs(const DavisScratch &s, uint64_t n, int bits, hipStream_t stream) {
-    size_t temp_bytes = s.temp_bytes;
-    hipcub::DoubleBuffer<uint32_t> k(s.keys0, s.keys1), v(s.idx0, s.idx1);
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(s.temp, temp_bytes, k, v, (int)n, 0, bits, stream);
-    if (e != hipSuccess) return e;
-    if (k.Current() != s.keys0) {
-        e = hipMemcpyAsync(s.keys0, k.Current(), n * 4u, hipMemcpyDeviceToDevice, stream);
-        if (e != hipSuccess) return e;
-    }
-    if (v.Current() != s.idx0) e = hipMemcpyAsync(s.idx0, v.Current(), n * 4u, hipMemcpyDeviceToDevice, stream);
-    return e;
-}
-
 hipError_t davis_generate(const DavisArgs &a, const DavisPacket &pk, const DavisPlanes &work, const DavisScratch &s,
                           AdderSparseStep *d_steps, uint8_t *d_img, hipStream_t stream) {
     hipLaunchKernelGGL(davis_init_scalars_kernel, dim3(1), dim3(1), 0, stream, s.sc);
     const bool raw = a.mode != ADDER_DAVIS_FRAMED;
     const uint64_t n = raw ? pk.n_held + pk.n_before : 0u;
     const uint32_t pgrid = grid_of(a.units);
+    const ChainScratch &c = s.chain;
     hipError_t e = hipSuccess;
-    size_t temp_bytes = s.temp_bytes;
     if (raw && n + pk.n_after > 0u)
-        hipLaunchKernelGGL(davis_chunk_keys_kernel, dim3(grid_of(n + pk.n_after)), dim3(256), 0, stream, a, pk, n, s.keys0,
-                           s.idx0, s.sc);
+        hipLaunchKernelGGL(davis_chunk_keys_kernel, dim3(grid_of(n + pk.n_after)), dim3(256), 0, stream, a, pk, n, c.keys0,
+                           c.idx0, s.sc);
     if (n > 0u) {
         const uint32_t grid = grid_of(n);
-        if ((e = sort_pairs(s, n, 4, stream)) != hipSuccess) return e;
+        if ((e = chain_sort_pairs(c, n, 4, stream)) != hipSuccess) return e;
         // keys0 = the sorted chunk keys, idx0 = the step order; both are sorted over again below
-        if ((e = hipMemcpyAsync(s.order, s.idx0, n * 4u, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(s.cnt, s.keys0, n * 4u, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(davis_pixel_keys_kernel, dim3(grid), dim3(256), 0, stream, a, pk, n, s.cnt, s.order, s.keys0,
-                           s.idx0);
-        if ((e = sort_pairs(s, n, (int)a.key_bits, stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(davis_gather_kernel, dim3(grid), dim3(256), 0, stream, a, pk, n, s.keys0, s.idx0, s.order,
+        if ((e = hipMemcpyAsync(s.order, c.idx0, n * 4u, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(c.cnt, c.keys0, n * 4u, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(davis_pixel_keys_kernel, dim3(grid), dim3(256), 0, stream, a, pk, n, c.cnt, s.order, c.keys0,
+                           c.idx0);
+        if ((e = chain_sort_pairs(c, n, (int)a.key_bits, stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(davis_gather_kernel, dim3(grid), dim3(256), 0, stream, a, pk, n, c.keys0, c.idx0, s.order,
                            s.sorted);
-        hipLaunchKernelGGL(davis_walk_kernel, dim3(grid), dim3(256), 0, stream, a, pk, n, work, s.keys0, s.idx0, s.sorted,
-                           s.cnt, s.stage);
-        e = hipcub::DeviceScan::ExclusiveSum(s.temp, temp_bytes, s.cnt, s.offs, (int)n, stream);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(davis_total_kernel, dim3(1), dim3(1), 0, stream, s.cnt, s.offs, n, s.sc);
-        hipLaunchKernelGGL(davis_scatter_kernel, dim3(grid), dim3(256), 0, stream, n, s.cnt, s.offs, s.stage, d_steps);
+        hipLaunchKernelGGL(davis_walk_kernel, dim3(grid), dim3(256), 0, stream, a, pk, n, work, c.keys0, c.idx0, s.sorted,
+                           c.cnt, c.stage);
+        if ((e = chain_scan_counts(c, n, &s.sc->ev_steps, stream)) != hipSuccess) return e;
+        if ((e = chain_scatter(c, n, d_steps, stream)) != hipSuccess) return e;
     }
     if (raw) {
         hipLaunchKernelGGL(davis_gaps_kernel, dim3(pgrid), dim3(256), 0, stream, a, pk, work, s.gcnt, s.gstage);
-        temp_bytes = s.temp_bytes;
-        e = hipcub::DeviceScan::ExclusiveSum(s.temp, temp_bytes, s.gcnt, s.goffs, (int)a.units, stream);
-        if (e != hipSuccess) return e;
+        if ((e = chain_exclusive_sum(c, s.gcnt, s.goffs, a.units, stream)) != hipSuccess) return e;
         hipLaunchKernelGGL(davis_gap_scatter_kernel, dim3(pgrid), dim3(256), 0, stream, a, s.gcnt, s.goffs, s.gstage, d_steps,
                            s.sc);
     }

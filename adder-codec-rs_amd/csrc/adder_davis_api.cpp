@@ -9,9 +9,9 @@
 #include <vector>
 
 #include "../../include/adder_davis.h"
-#include "adder_api_util.hpp"
 #include "adder_davis_kernels.h"
 #include "adder_davis_logic.hpp"
+#include "adder_source_util.hpp"
 
 using namespace adder;
 
@@ -20,10 +20,6 @@ static thread_local std::string g_davis_create_error;
 namespace {
 
 enum Phase { kOpen = 0, kFinished = 1 };
-
-// Crf rows 0..9: baseline C, max C, C increase velocity (rate_controller.rs; the same table as the C++ mirror's)
-const uint8_t kCrf[10][3] = {{0, 0, 10}, {0, 1, 9}, {1, 3, 8}, {2, 7, 7},  {5, 9, 6},
-                             {6, 10, 5}, {7, 13, 4}, {8, 16, 3}, {10, 20, 2}, {15, 25, 1}};
 
 }  // namespace
 
@@ -44,11 +40,9 @@ struct AdderDavis {
     // the previous packet's `after` events (device), and a second buffer the next ones are copied into
     AdderDavisEvent *held = nullptr, *held2 = nullptr;
     uint64_t held_n = 0, held_cap = 0, held2_cap = 0;
-    // push scratch for `cap` list events
-    uint64_t cap = 0;
-    DavisScratch s{};
-    AdderSparseStep *steps = nullptr;
-    uint64_t steps_cap = 0;
+    DavisScratch s{};  // push scratch
+    size_t order_bytes = 0, sorted_bytes = 0;  // of s.order and s.sorted, which follow s.chain.cap
+    StepBuffer steps;
     uint8_t *img = nullptr;        // Framed: image_8u
     uint64_t *frame_offs = nullptr;  // Framed: the dense batch's two offsets
     DavisScalars *h_sc = nullptr;  // pinned
@@ -69,27 +63,15 @@ static int dfail(AdderDavis *v, int code, const char *fmt, ...) {
 #define DHIPCHK(v, expr) ADDER_HIPCHK(dfail, v, expr, #expr)
 
 // ------------------------------------------------------------------------------------------ lifecycle
-static void free_scratch(AdderDavis *v) {
-    api_free_all({v->s.keys0, v->s.keys1, v->s.idx0, v->s.idx1, v->s.order, v->s.sorted, v->s.cnt, v->s.offs, v->s.stage,
-                  v->s.temp});
-    DavisScratch keep = v->s;
-    v->s = DavisScratch{};
-    v->s.gcnt = keep.gcnt;
-    v->s.goffs = keep.goffs;
-    v->s.gstage = keep.gstage;
-    v->s.sc = keep.sc;
-    v->cap = 0;
-}
-
 static void davis_free(AdderDavis *v) {
     if (!v) return;
     (void)hipSetDevice(v->p.device_id);
     if (v->stream) (void)hipStreamSynchronize(v->stream);
     (void)hipDeviceSynchronize();
-    free_scratch(v);
-    api_free_all({v->planes[0].ts, v->planes[0].ln, v->planes[1].ts, v->planes[1].ln, v->s.gcnt, v->s.goffs, v->s.gstage,
-                  v->s.sc, v->held, v->held2, v->steps, v->img, v->frame_offs, v->d_frame, v->d_before, v->d_after,
-                  v->d_out});
+    chain_free(v->s.chain);
+    api_free_all({v->planes[0].ts, v->planes[0].ln, v->planes[1].ts, v->planes[1].ln, v->s.order, v->s.sorted, v->s.gcnt,
+                  v->s.goffs, v->s.gstage, v->s.sc, v->held, v->held2, v->steps.p, v->img, v->frame_offs, v->d_frame,
+                  v->d_before, v->d_after, v->d_out});
     if (v->h_sc) (void)hipHostFree(v->h_sc);
     if (v->ctx) adder_hip_destroy(v->ctx);
     if (v->stream) (void)hipStreamDestroy(v->stream);
@@ -99,32 +81,17 @@ static void davis_free(AdderDavis *v) {
 // Davis::new (davis.rs:109-177) + time_parameters + .crf(c) as the mirror's Video makes its context; the camera state
 // back to last ts = 0, last ln = 0.0
 static int open_ctx(AdderDavis *v) {
-    if (v->ctx) adder_hip_destroy(v->ctx);
-    v->ctx = nullptr;
     const AdderDavisParams &p = v->p;
     AdderHipParams hp;
     adder_hip_default_params(&hp, p.width, p.height, 1);
-    hp.time_mode = ADDER_TIME_ABSOLUTE_T;
-    hp.multi_mode = ADDER_MULTI_COLLAPSE;
     hp.pixel_mode = p.mode == ADDER_DAVIS_FRAMED ? ADDER_MODE_FRAME_PERFECT : ADDER_MODE_CONTINUOUS;
     hp.ref_time = p.ref_time;
     hp.delta_t_max = p.delta_t_max;
-    if (p.crf != ADDER_DAVIS_NO_CRF) {
-        hp.c_thresh_max = kCrf[p.crf][1];
-        hp.c_increase_velocity = kCrf[p.crf][2];
-    }
     hp.chunk_rows = p.height / 4u;
     hp.device_id = p.device_id;
-    int rc = adder_hip_create(&hp, &v->ctx);
-    if (rc != ADDER_OK) {
-        v->ctx = nullptr;
-        return dfail(v, rc, "inner context: %s", adder_hip_last_error(nullptr));
-    }
-    if (p.crf != ADDER_DAVIS_NO_CRF && (rc = adder_hip_reset_c_thresh(v->ctx, kCrf[p.crf][0])) != ADDER_OK)
-        return dfail(v, rc, "reset_c_thresh: %s", adder_hip_last_error(v->ctx));
-    if ((rc = adder_hip_enable_running_intensities(v->ctx, 1)) != ADDER_OK)
-        return dfail(v, rc, "enable_running_intensities: %s", adder_hip_last_error(v->ctx));
-    v->eps = adder_hip_max_events_per_frame(v->ctx) / v->a.units;
+    // ADDER_DAVIS_NO_CRF (-1) leaves the context's default limits and baseline alone
+    const int rc = source_open_ctx(&v->ctx, hp, p.crf, p.crf, v->a.units, &v->eps, v->err);
+    if (rc != ADDER_OK) return rc;
     const size_t u = v->a.units;
     DHIPCHK(v, hipMemsetAsync(v->planes[0].ts, 0, u * 8u, v->stream));
     DHIPCHK(v, hipMemsetAsync(v->planes[0].ln, 0, u * 8u, v->stream));  // 0.0
@@ -154,11 +121,7 @@ extern "C" int adder_davis_create(const AdderDavisParams *p, AdderDavis **out) {
         return dfail(nullptr, ADDER_E_BAD_PARAMS, "tps %u, ref_time %u, delta_t_max %u", p->tps, p->ref_time, p->delta_t_max);
     if (p->crf != ADDER_DAVIS_NO_CRF && (p->crf < 0 || p->crf > 9))
         return dfail(nullptr, ADDER_E_BAD_PARAMS, "crf %d (0..9, or ADDER_DAVIS_NO_CRF)", p->crf);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return dfail(nullptr, ADDER_E_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (p->device_id < 0 || p->device_id >= ndev)
-        return dfail(nullptr, ADDER_E_BAD_PARAMS, "device_id %d of %d", p->device_id, ndev);
+    if (const int rc = api_check_device(p->device_id, g_davis_create_error)) return rc;
     AdderDavis *v = new (std::nothrow) AdderDavis();
     if (!v) return dfail(nullptr, ADDER_E_BAD_PARAMS, "out of host memory");
     v->p = *p;
@@ -167,8 +130,7 @@ extern "C" int adder_davis_create(const AdderDavisParams *p, AdderDavis **out) {
     a.height = p->height;
     a.units = (uint32_t)p->width * p->height;
     a.chunk_h = p->height / 4u;
-    a.key_bits = 1;
-    while ((1ull << a.key_bits) < (uint64_t)a.units + 1u) ++a.key_bits;
+    a.key_bits = key_bits_for(a.units);
     a.mode = p->mode;
     a.tps = p->tps;
     a.ref_time = p->ref_time;
@@ -244,40 +206,13 @@ extern "C" int adder_davis_running_intensities(AdderDavis *v, uint8_t *dst) {
 }
 
 // ------------------------------------------------------------------------------------------ push, finish
-static int ensure_steps(AdderDavis *v, uint64_t n) {
-    if (n <= v->steps_cap) return ADDER_OK;
-    if (v->steps) DHIPCHK(v, hipFree(v->steps));
-    v->steps = nullptr;
-    v->steps_cap = 0;
-    DHIPCHK(v, hipMalloc((void **)&v->steps, n * sizeof(AdderSparseStep)));
-    v->steps_cap = n;
-    return ADDER_OK;
-}
-
 static int ensure_scratch(AdderDavis *v, uint64_t n) {
-    if (n > v->cap) {
-        free_scratch(v);
-        const uint64_t c = n + n / 8u > (uint64_t)INT32_MAX ? (uint64_t)INT32_MAX : n + n / 8u;
-        DHIPCHK(v, hipMalloc((void **)&v->s.keys0, c * 4u));
-        DHIPCHK(v, hipMalloc((void **)&v->s.keys1, c * 4u));
-        DHIPCHK(v, hipMalloc((void **)&v->s.idx0, c * 4u));
-        DHIPCHK(v, hipMalloc((void **)&v->s.idx1, c * 4u));
-        DHIPCHK(v, hipMalloc((void **)&v->s.order, c * 4u));
-        DHIPCHK(v, hipMalloc((void **)&v->s.sorted, c * sizeof(DavisWalkEvent)));
-        DHIPCHK(v, hipMalloc((void **)&v->s.cnt, c * 4u));
-        DHIPCHK(v, hipMalloc((void **)&v->s.offs, c * 4u));
-        DHIPCHK(v, hipMalloc((void **)&v->s.stage, c * 2u * sizeof(AdderSparseStep)));
-        v->cap = c;
-    }
-    const size_t need = davis_temp_bytes(v->cap, v->a.units);
-    if (need > v->s.temp_bytes) {
-        if (v->s.temp) DHIPCHK(v, hipFree(v->s.temp));
-        v->s.temp = nullptr;
-        v->s.temp_bytes = 0;
-        DHIPCHK(v, hipMalloc(&v->s.temp, need));
-        v->s.temp_bytes = need;
-    }
-    return ensure_steps(v, 2u * v->cap + 2u * (uint64_t)v->a.units);
+    DavisScratch &s = v->s;
+    DHIPCHK(v, chain_reserve(s.chain, n, v->a.units));  // before any list came: the gap scan's temp alone
+    DHIPCHK(v, api_grow((void **)&s.order, &v->order_bytes, s.chain.cap * 4u));
+    DHIPCHK(v, api_grow((void **)&s.sorted, &v->sorted_bytes, s.chain.cap * sizeof(DavisWalkEvent)));
+    DHIPCHK(v, steps_reserve(v->steps, 2u * s.chain.cap + 2u * (uint64_t)v->a.units));
+    return ADDER_OK;
 }
 
 static int push(AdderDavis *v, const double *d_frame, const AdderDavisMeta *meta, const AdderDavisEvent *d_before,
@@ -328,7 +263,7 @@ static int push(AdderDavis *v, const double *d_frame, const AdderDavisMeta *meta
     const size_t u = v->a.units;
     DHIPCHK(v, hipMemcpyAsync(work.ts, cur.ts, u * 8u, hipMemcpyDeviceToDevice, s));
     DHIPCHK(v, hipMemcpyAsync(work.ln, cur.ln, u * 8u, hipMemcpyDeviceToDevice, s));
-    DHIPCHK(v, davis_generate(v->a, pk, work, v->s, v->steps, v->img, s));
+    DHIPCHK(v, davis_generate(v->a, pk, work, v->s, v->steps.p, v->img, s));
     DHIPCHK(v, hipMemcpyAsync(v->h_sc, v->s.sc, sizeof(DavisScalars), hipMemcpyDeviceToHost, s));
     // the new `after` events go to the spare buffer meanwhile; it becomes the held one only if the push is accepted
     if (raw && n_after) {
@@ -359,12 +294,12 @@ static int push(AdderDavis *v, const double *d_frame, const AdderDavisMeta *meta
         // the lists' and the gaps' steps, then the frame's: two calls, so that the frame's events can be told apart
         const uint64_t head = sc.ev_steps + sc.gap_steps;
         if (head) {
-            rc = adder_hip_integrate_sparse_device(v->ctx, v->steps, head, d_out, out_cap, &got, s);
+            rc = adder_hip_integrate_sparse_device(v->ctx, v->steps.p, head, d_out, out_cap, &got, s);
             total = got;
         }
         if (rc == ADDER_OK) {
             got = 0;
-            rc = adder_hip_integrate_sparse_device(v->ctx, v->steps + head, u, d_out + total, out_cap - total, &got, s);
+            rc = adder_hip_integrate_sparse_device(v->ctx, v->steps.p + head, u, d_out + total, out_cap - total, &got, s);
             total += got;
             v->last_frame_events = got;
         }
@@ -449,11 +384,10 @@ extern "C" int adder_davis_finish_device(AdderDavis *v, AdderEvent *d_out, uint6
     }
     DHIPCHK(v, hipSetDevice(v->p.device_id));
     const hipStream_t s = (hipStream_t)stream;
-    int rc = ensure_steps(v, v->a.units);
-    if (rc != ADDER_OK) return rc;
-    DHIPCHK(v, davis_flush_steps(v->a, v->steps, s));
+    DHIPCHK(v, steps_reserve(v->steps, v->a.units));
+    DHIPCHK(v, davis_flush_steps(v->a, v->steps.p, s));
     size_t got = 0;
-    rc = adder_hip_integrate_sparse_device(v->ctx, v->steps, v->a.units, d_out, out_cap, &got, s);
+    const int rc = adder_hip_integrate_sparse_device(v->ctx, v->steps.p, v->a.units, d_out, out_cap, &got, s);
     v->phase = kFinished;
     if (rc != ADDER_OK) return dfail(v, rc, "integrate_sparse: %s", adder_hip_last_error(v->ctx));
     v->held_n = 0;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/adder_davis.h"
+#include "adder_chain_kernels.h"
 
 namespace adder {
 
@@ -43,20 +44,15 @@ struct DavisWalkEvent {  // an event as the walk reads it: its pixel's events si
     uint32_t flags;  // bit 0: on; bit 1: the last event of its pixel
 };
 
-struct DavisScratch {  // for `cap` list events (held + before) and the plane
-    uint32_t *keys0, *keys1, *idx0, *idx1;  // cap each
-    uint32_t *order;          // step rank -> list index (held events first)
-    DavisWalkEvent *sorted;   // by pixel, then step rank
-    uint32_t *cnt, *offs;     // by step rank: steps of the event (0 or 2), their exclusive scan
-    AdderSparseStep *stage;   // by step rank: two slots per event
+struct DavisScratch {
+    ChainScratch chain;       // for chain.cap list events (held + before); cnt, offs and stage by step rank
+    uint32_t *order;          // chain.cap: step rank -> list index (held events first)
+    DavisWalkEvent *sorted;   // chain.cap: by pixel, then step rank
     uint32_t *gcnt, *goffs;   // by pixel: gap steps (0 or 1), their exclusive scan
     AdderSparseStep *gstage;  // by pixel
-    void *temp;
-    size_t temp_bytes;
     DavisScalars *sc;
 };
 
-size_t davis_temp_bytes(uint64_t n_events, uint32_t units);
 // One packet on the `work` planes (a copy of the committed ones, made by the caller): checks, the two lists' steps,
 // the gaps, the frame.  d_steps receives ev_steps + gap_steps + units steps in the raw modes (room: 2 * (n_held +
 // n_before) + 2 * units); Framed only writes d_img (units bytes) and the planes.  The caller reads s.sc afterwards.

@@ -81,7 +81,7 @@ static void dvs_free(AdderDvs *v) {
 static int ensure_scratch(AdderDvs *v, uint64_t n) {
     if (n <= v->cap) return ADDER_OK;
     free_scratch(v);
-    const uint64_t c = n + n / 8u > (uint64_t)INT32_MAX ? (uint64_t)INT32_MAX : n + n / 8u;
+    const uint64_t c = scratch_capacity(n);
     DHIPCHK(v, hipMalloc((void **)&v->s.keys0, c * 4u));
     DHIPCHK(v, hipMalloc((void **)&v->s.keys1, c * 4u));
     DHIPCHK(v, hipMalloc((void **)&v->s.idx0, c * 4u));
@@ -137,8 +137,7 @@ extern "C" int adder_dvs_create(const AdderDvsParams *p, AdderDvs **out) {
     a.height = p->height;
     a.channels = p->channels;
     a.units = (uint32_t)p->width * p->height * p->channels;
-    a.key_bits = 1;
-    while ((1ull << a.key_bits) < (uint64_t)a.units + 1u) ++a.key_bits;  // keys 0..units (units: never walked)
+    a.key_bits = key_bits_for(a.units);  // keys 0..units (units: never walked)
     a.delta_t = p->time_mode == 0 ? 1u : 0u;
     a.framed = p->source_camera <= 5u ? 1u : 0u;  // is_framed (lib.rs:50-60): FramedU8 .. FramedF64
     a.ref = p->ref_interval;

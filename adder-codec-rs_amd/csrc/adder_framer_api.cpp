@@ -625,10 +625,8 @@ static int ingest_with_features(AdderFramer *fr, const AdderEvent *d_events, con
     st.out = fr->feat_out;
     st.out_cap = n;
     st.count = fr->feat_count;
-    uint32_t key_bits = 0;
-    while (((uint64_t)1 << key_bits) < (uint64_t)fr->n_units + 1u) ++key_bits;
     FHIPCHK(fr, framer_features_run(reinterpret_cast<const uint32_t *>(d_events + e0), n, e0 + fr->feat_index_bias, a,
-                                    key_bits, sc, st, s));
+                                    key_bits_for(fr->n_units), sc, st, s));
     fr->feat_pending = true;
     fr->feat_fw = fr->frames_written;
     return mark_op(fr, s);

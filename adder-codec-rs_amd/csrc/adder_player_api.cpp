@@ -139,8 +139,7 @@ extern "C" int adder_player_create(const AdderPlayerParams *p, AdderPlayer **out
     a.height = p->height;
     a.channels = p->channels;
     a.units = (uint32_t)p->width * p->height * p->channels;
-    a.key_bits = 1;
-    while ((1ull << a.key_bits) < (uint64_t)a.units + 1u) ++a.key_bits;  // keys 0..units (units: takes part in nothing)
+    a.key_bits = key_bits_for(a.units);  // keys 0..units (units: takes part in nothing)
     a.absolute = p->time_mode == ADDER_TIME_ABSOLUTE_T ? 1u : 0u;
     a.ref = p->ref_interval;
     a.out_type = p->out_type;

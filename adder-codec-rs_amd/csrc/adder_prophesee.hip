@@ -6,12 +6,12 @@
 //      and sorted behind every pixel); a stable radix sort brings a pixel's records together in camera order;
 //   2. walk: a thread per run chains the pixel's last t and log intensity and writes each record's zero, one or two
 //      steps into the record's two slots (input order), exps evaluated on the chain;
-//   3. an exclusive scan of the step counts in input order places the steps, a thread per record copies them;
+//   3. an exclusive scan of the step counts in input order places the steps, a thread per record copies them
+//      (the sort, the scan and the copy are adder_chain.hip's, shared with adder_davis.hip);
 //   4. commit: the walked pixels' state is copied back -- only after the host has checked the bad-record word and
 //      the output room, so a refused push changes nothing.
 // The steps then go to adder_hip_integrate_sparse_device unchanged.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 #include "adder_exp.hpp"
@@ -121,22 +121,6 @@ __global__ __launch_bounds__(256) void pph_walk_kernel(const uint8_t *__restrict
     a.nxt_ln[u] = ln;
 }
 
-__global__ void pph_total_kernel(const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ offs, uint64_t n,
-                                 PphScalars *sc) {
-    sc->steps = (unsigned long long)offs[n - 1] + cnt[n - 1];
-}
-
-__global__ __launch_bounds__(256) void pph_scatter_kernel(uint64_t n, const uint32_t *__restrict__ cnt,
-                                                          const uint32_t *__restrict__ offs,
-                                                          const AdderSparseStep *__restrict__ stage,
-                                                          AdderSparseStep *__restrict__ steps) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t c = cnt[i];
-    const uint64_t o = offs[i];
-    for (uint32_t k = 0; k < c; ++k) steps[o + k] = stage[2u * i + k];
-}
-
 __global__ __launch_bounds__(256) void pph_commit_kernel(uint64_t n, PphArgs a, const uint32_t *__restrict__ keys) {
     const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (j >= n) return;
@@ -176,43 +160,23 @@ __global__ __launch_bounds__(256) void pph_exp_kernel(const double *__restrict__
     if (i < n) y[i] = adder_exp(x[i]);
 }
 
-static uint32_t grid_of(uint64_t n) { return (uint32_t)((n + 255u) / 256u); }
-
-size_t pph_temp_bytes(uint64_t n) {
-    size_t a = 0, b = 0;
-    hipcub::DoubleBuffer<uint32_t> k(nullptr, nullptr), v(nullptr, nullptr);
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, k, v, (int)n);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n);
-    return (a > b ? a : b) + 256;
-}
-
 hipError_t pph_generate(const PphArgs &a, const uint8_t *rec, uint64_t n, const PphScratch &s, hipStream_t stream) {
     hipLaunchKernelGGL(pph_init_scalars_kernel, dim3(1), dim3(1), 0, stream, s.sc);
     if (n == 0u) return hipGetLastError();
     const uint32_t grid = grid_of(n);
-    size_t temp_bytes = s.temp_bytes;
-    hipLaunchKernelGGL(pph_keys_kernel, dim3(grid), dim3(256), 0, stream, rec, n, a, s.keys0, s.idx0, s.sc);
-    hipcub::DoubleBuffer<uint32_t> k(s.keys0, s.keys1), v(s.idx0, s.idx1);
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(s.temp, temp_bytes, k, v, (int)n, 0, (int)a.key_bits, stream);
+    const ChainScratch &c = s.chain;
+    hipLaunchKernelGGL(pph_keys_kernel, dim3(grid), dim3(256), 0, stream, rec, n, a, c.keys0, c.idx0, s.sc);
+    const hipError_t e = chain_sort_pairs(c, n, (int)a.key_bits, stream);
     if (e != hipSuccess) return e;
-    // the sorted keys / indices end in keys0 / idx0 for the emit step
-    if (k.Current() != s.keys0) {
-        e = hipMemcpyAsync(s.keys0, k.Current(), n * 4u, hipMemcpyDeviceToDevice, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(s.idx0, v.Current(), n * 4u, hipMemcpyDeviceToDevice, stream);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(pph_walk_kernel, dim3(grid), dim3(256), 0, stream, rec, n, a, s.keys0, s.idx0, s.cnt, s.stage);
-    e = hipcub::DeviceScan::ExclusiveSum(s.temp, temp_bytes, s.cnt, s.offs, (int)n, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pph_total_kernel, dim3(1), dim3(1), 0, stream, s.cnt, s.offs, n, s.sc);
-    return hipGetLastError();
+    hipLaunchKernelGGL(pph_walk_kernel, dim3(grid), dim3(256), 0, stream, rec, n, a, c.keys0, c.idx0, c.cnt, c.stage);
+    return chain_scan_counts(c, n, &s.sc->steps, stream);
 }
 
 hipError_t pph_emit(const PphArgs &a, uint64_t n, const PphScratch &s, AdderSparseStep *d_steps, hipStream_t stream) {
     if (n == 0u) return hipSuccess;
-    const uint32_t grid = grid_of(n);
-    hipLaunchKernelGGL(pph_scatter_kernel, dim3(grid), dim3(256), 0, stream, n, s.cnt, s.offs, s.stage, d_steps);
-    hipLaunchKernelGGL(pph_commit_kernel, dim3(grid), dim3(256), 0, stream, n, a, s.keys0);
+    const hipError_t e = chain_scatter(s.chain, n, d_steps, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pph_commit_kernel, dim3(grid_of(n)), dim3(256), 0, stream, n, a, s.chain.keys0);
     return hipGetLastError();
 }
 

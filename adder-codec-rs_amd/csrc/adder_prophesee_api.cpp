@@ -11,10 +11,10 @@
 #include <vector>
 
 #include "../../include/adder_prophesee.h"
-#include "adder_api_util.hpp"
 #include "adder_exp.hpp"
 #include "adder_log1p.hpp"
 #include "adder_prophesee_kernels.h"
+#include "adder_source_util.hpp"
 
 using namespace adder;
 
@@ -24,10 +24,6 @@ namespace {
 
 enum Phase { kCreated = 0, kStarted = 1, kFinished = 2 };
 constexpr uint32_t kPphMaxDepth = 31;  // kMaxDepthLimit (adder_pixel.hpp)
-
-// Crf rows 0..9: baseline C, max C, C increase velocity (rate_controller.rs; the same table as the C++ mirror's)
-const uint8_t kCrf[10][3] = {{0, 0, 10}, {0, 1, 9}, {1, 3, 8}, {2, 7, 7},  {5, 9, 6},
-                             {6, 10, 5}, {7, 13, 4}, {8, 16, 3}, {10, 20, 2}, {15, 25, 1}};
 
 // Rust's str::parse::<u32>: an optional '+', then decimal digits only, no overflow
 bool parse_u32(const uint8_t *s, size_t n, uint32_t *out) {
@@ -59,11 +55,8 @@ struct AdderProphesee {
     // the open group's records (device), and a second buffer of the same size to move the tail into
     uint8_t *pend = nullptr, *pend2 = nullptr;
     uint64_t pend_n = 0, pend_cap = 0;
-    // push scratch, for `cap` records
-    uint64_t cap = 0;
-    PphScratch s{};
-    AdderSparseStep *steps = nullptr;  // 2 * cap (and at least units, for end_events)
-    uint64_t steps_cap = 0;
+    PphScratch s{};    // push scratch
+    StepBuffer steps;  // 2 * s.chain.cap (and at least units, for end_events)
     PphScalars *h_sc = nullptr;        // pinned
     uint32_t *h_t = nullptr;           // pinned: the pushed records' t
     uint64_t h_t_cap = 0;
@@ -200,21 +193,13 @@ extern "C" uint64_t adder_prophesee_scan_groups(const uint8_t *records, uint64_t
 }
 
 // ------------------------------------------------------------------------------------------ lifecycle
-static void free_scratch(AdderProphesee *v) {
-    api_free_all({v->s.keys0, v->s.keys1, v->s.idx0, v->s.idx1, v->s.cnt, v->s.offs, v->s.stage, v->s.temp});
-    PphScalars *sc = v->s.sc;
-    v->s = PphScratch{};
-    v->s.sc = sc;
-    v->cap = 0;
-}
-
 static void pph_free(AdderProphesee *v) {
     if (!v) return;
     (void)hipSetDevice(v->p.device_id);
     if (v->stream) (void)hipStreamSynchronize(v->stream);
     (void)hipDeviceSynchronize();
-    free_scratch(v);
-    api_free_all({v->a.cur_t, v->a.nxt_t, v->a.cur_ln, v->a.nxt_ln, v->s.sc, v->pend, v->pend2, v->steps, v->d_in,
+    chain_free(v->s.chain);
+    api_free_all({v->a.cur_t, v->a.nxt_t, v->a.cur_ln, v->a.nxt_ln, v->s.sc, v->pend, v->pend2, v->steps.p, v->d_in,
                   v->d_out});
     if (v->h_sc) (void)hipHostFree(v->h_sc);
     if (v->h_t) (void)hipHostFree(v->h_t);
@@ -226,35 +211,21 @@ static void pph_free(AdderProphesee *v) {
 // Prophesee::new (:56-113) + .crf(c): a Continuous context with the source's time parameters; the camera state
 // back to last t = 2, last ln = ln_1p(128 / 255)
 static int open_ctx(AdderProphesee *v) {
-    if (v->ctx) adder_hip_destroy(v->ctx);
-    v->ctx = nullptr;
     const AdderPropheseeParams &p = v->p;
     AdderHipParams hp;
     adder_hip_default_params(&hp, p.width, p.height, 1);
-    hp.time_mode = ADDER_TIME_ABSOLUTE_T;
-    hp.multi_mode = ADDER_MULTI_COLLAPSE;
     hp.pixel_mode = ADDER_MODE_CONTINUOUS;
     hp.ref_time = p.ref_time;
     hp.delta_t_max = p.ref_time * 2u;
-    const int q = p.crf == ADDER_PROPHESEE_NO_CRF ? 3 : p.crf;  // Crf::new(None) is quality 3
-    hp.c_thresh_max = kCrf[q][1];
-    hp.c_increase_velocity = kCrf[q][2];
     hp.chunk_rows = 1;
     // the reference's arena grows without bound; a camera pixel at crf 0 (c_thresh 0) stores more than the framed
     // default of 16 nodes, so the context takes the largest depth the kernels support
     hp.max_depth = kPphMaxDepth;
     hp.device_id = p.device_id;
-    int rc = adder_hip_create(&hp, &v->ctx);
-    if (rc != ADDER_OK) {
-        v->ctx = nullptr;
-        return pfail(v, rc, "inner context: %s", adder_hip_last_error(nullptr));
-    }
-    if (p.crf != ADDER_PROPHESEE_NO_CRF && (rc = adder_hip_reset_c_thresh(v->ctx, kCrf[q][0])) != ADDER_OK)
-        return pfail(v, rc, "reset_c_thresh: %s", adder_hip_last_error(v->ctx));
-    if ((rc = adder_hip_enable_running_intensities(v->ctx, 1)) != ADDER_OK)
-        return pfail(v, rc, "enable_running_intensities: %s", adder_hip_last_error(v->ctx));
-    // a Continuous context bounds a frame at units * (max_depth + 3) events: the sparse integrator's bound per step
-    v->eps = adder_hip_max_events_per_frame(v->ctx) / v->a.units;
+    // Crf::new(None) is quality 3: its limits hold, but without a .crf(c) call no pixel is reset to its baseline
+    const int rc = source_open_ctx(&v->ctx, hp, p.crf == ADDER_PROPHESEE_NO_CRF ? 3 : p.crf,
+                                   p.crf == ADDER_PROPHESEE_NO_CRF ? -1 : p.crf, v->a.units, &v->eps, v->err);
+    if (rc != ADDER_OK) return rc;
     PHIPCHK(v, pph_init_state(v->a, v->stream));
     PHIPCHK(v, hipStreamSynchronize(v->stream));
     v->phase = kCreated;
@@ -274,11 +245,7 @@ extern "C" int adder_prophesee_create(const AdderPropheseeParams *p, AdderProphe
         return pfail(nullptr, ADDER_E_BAD_PARAMS, "ref_time %u (1 .. 2^31 - 1)", p->ref_time);
     if (p->crf != ADDER_PROPHESEE_NO_CRF && (p->crf < 0 || p->crf > 9))
         return pfail(nullptr, ADDER_E_BAD_PARAMS, "crf %d (0..9, or ADDER_PROPHESEE_NO_CRF)", p->crf);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return pfail(nullptr, ADDER_E_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (p->device_id < 0 || p->device_id >= ndev)
-        return pfail(nullptr, ADDER_E_BAD_PARAMS, "device_id %d of %d", p->device_id, ndev);
+    if (const int rc = api_check_device(p->device_id, g_pph_create_error)) return rc;
     AdderProphesee *v = new (std::nothrow) AdderProphesee();
     if (!v) return pfail(nullptr, ADDER_E_BAD_PARAMS, "out of host memory");
     v->p = *p;
@@ -286,8 +253,7 @@ extern "C" int adder_prophesee_create(const AdderPropheseeParams *p, AdderProphe
     a.width = p->width;
     a.height = p->height;
     a.units = (uint32_t)p->width * p->height;
-    a.key_bits = 1;
-    while ((1ull << a.key_bits) < (uint64_t)a.units + 1u) ++a.key_bits;
+    a.key_bits = key_bits_for(a.units);
     a.ref_time = p->ref_time;
     a.theta = 0.02;  // camera_theta (:108)
     a.ln_mid = dvs_log1p(128.0 / 255.0);
@@ -386,31 +352,10 @@ extern "C" int adder_prophesee_start(AdderProphesee *v, AdderEvent *out, uint64_
     return ADDER_OK;
 }
 
-static int ensure_steps(AdderProphesee *v, uint64_t n) {
-    if (n <= v->steps_cap) return ADDER_OK;
-    if (v->steps) PHIPCHK(v, hipFree(v->steps));
-    v->steps = nullptr;
-    v->steps_cap = 0;
-    PHIPCHK(v, hipMalloc((void **)&v->steps, n * sizeof(AdderSparseStep)));
-    v->steps_cap = n;
-    return ADDER_OK;
-}
-
 static int ensure_scratch(AdderProphesee *v, uint64_t n) {
-    if (n <= v->cap) return ADDER_OK;
-    free_scratch(v);
-    const uint64_t c = n + n / 8u > (uint64_t)INT32_MAX ? (uint64_t)INT32_MAX : n + n / 8u;
-    PHIPCHK(v, hipMalloc((void **)&v->s.keys0, c * 4u));
-    PHIPCHK(v, hipMalloc((void **)&v->s.keys1, c * 4u));
-    PHIPCHK(v, hipMalloc((void **)&v->s.idx0, c * 4u));
-    PHIPCHK(v, hipMalloc((void **)&v->s.idx1, c * 4u));
-    PHIPCHK(v, hipMalloc((void **)&v->s.cnt, c * 4u));
-    PHIPCHK(v, hipMalloc((void **)&v->s.offs, c * 4u));
-    PHIPCHK(v, hipMalloc((void **)&v->s.stage, c * 2u * sizeof(AdderSparseStep)));
-    v->s.temp_bytes = pph_temp_bytes(c);
-    PHIPCHK(v, hipMalloc(&v->s.temp, v->s.temp_bytes));
-    v->cap = c;
-    return ensure_steps(v, 2u * c);
+    PHIPCHK(v, chain_reserve(v->s.chain, n, 0u));
+    PHIPCHK(v, steps_reserve(v->steps, 2u * v->s.chain.cap));
+    return ADDER_OK;
 }
 
 // the open group's buffers hold `need` records; the carried ones are kept
@@ -457,8 +402,8 @@ static int push(AdderProphesee *v, const uint8_t *d_rec, const uint8_t *h_rec, u
         }
         int rc_ = ensure_scratch(v, n);  // keys0 holds the records' t for the copy
         if (rc_ != ADDER_OK) return rc_;
-        PHIPCHK(v, pph_times(d_rec, n, v->s.keys0, s));
-        PHIPCHK(v, hipMemcpyAsync(v->h_t, v->s.keys0, n * 4u, hipMemcpyDeviceToHost, s));
+        PHIPCHK(v, pph_times(d_rec, n, v->s.chain.keys0, s));
+        PHIPCHK(v, hipMemcpyAsync(v->h_t, v->s.chain.keys0, n * 4u, hipMemcpyDeviceToHost, s));
         PHIPCHK(v, hipStreamSynchronize(s));
         done = scan_groups<4>((const uint8_t *)v->h_t, n, &start, &rt, nullptr);
     }
@@ -485,10 +430,10 @@ static int push(AdderProphesee *v, const uint8_t *d_rec, const uint8_t *h_rec, u
             return pfail(v, ADDER_E_OUT_CAPACITY, "%llu steps may make %llu events; the buffer holds %llu",
                          (unsigned long long)sc.steps, (unsigned long long)need, (unsigned long long)out_cap);
         }
-        PHIPCHK(v, pph_emit(v->a, m, v->s, v->steps, s));
+        PHIPCHK(v, pph_emit(v->a, m, v->s, v->steps.p, s));
         if (sc.steps) {
             size_t got = 0;
-            rc = adder_hip_integrate_sparse_device(v->ctx, v->steps, sc.steps, d_out, out_cap, &got, s);
+            rc = adder_hip_integrate_sparse_device(v->ctx, v->steps.p, sc.steps, d_out, out_cap, &got, s);
             if (rc != ADDER_OK) {
                 v->phase = kFinished;  // the pixels have been stepped: only reset helps
                 return pfail(v, rc, "integrate_sparse: %s", adder_hip_last_error(v->ctx));
@@ -555,9 +500,8 @@ extern "C" int adder_prophesee_finish_device(AdderProphesee *v, AdderEvent *d_ou
     }
     PHIPCHK(v, hipSetDevice(v->p.device_id));
     const hipStream_t s = (hipStream_t)stream;
-    int rc = ensure_steps(v, v->a.units);
-    if (rc != ADDER_OK) return rc;
-    PHIPCHK(v, pph_end_steps(v->a, v->running_t, v->steps, v->s.sc, s));
+    PHIPCHK(v, steps_reserve(v->steps, v->a.units));
+    PHIPCHK(v, pph_end_steps(v->a, v->running_t, v->steps.p, v->s.sc, s));
     PHIPCHK(v, hipMemcpyAsync(v->h_sc, v->s.sc, sizeof(PphScalars), hipMemcpyDeviceToHost, s));
     PHIPCHK(v, hipStreamSynchronize(s));
     if (v->h_sc->end_bad) {
@@ -566,7 +510,7 @@ extern "C" int adder_prophesee_finish_device(AdderProphesee *v, AdderEvent *d_ou
                      "reference asserts running_t - last_t > 0", (unsigned long long)v->h_sc->end_bad, v->running_t);
     }
     size_t got = 0;
-    rc = adder_hip_integrate_sparse_device(v->ctx, v->steps, v->a.units, d_out, out_cap, &got, s);
+    const int rc = adder_hip_integrate_sparse_device(v->ctx, v->steps.p, v->a.units, d_out, out_cap, &got, s);
     v->phase = kFinished;
     if (rc != ADDER_OK) return pfail(v, rc, "integrate_sparse: %s", adder_hip_last_error(v->ctx));
     v->pend_n = 0;  // the open group is dropped

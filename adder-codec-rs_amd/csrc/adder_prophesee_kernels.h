@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/adder_hip.h"
+#include "adder_chain_kernels.h"
 
 namespace adder {
 
@@ -25,17 +25,11 @@ struct PphArgs {
     double *cur_ln, *nxt_ln;
 };
 
-struct PphScratch {  // per push, for n records
-    uint32_t *keys0, *keys1, *idx0, *idx1;
-    uint32_t *cnt;            // input order: steps of the record (0..2)
-    uint32_t *offs;           // input order: exclusive scan of cnt
-    AdderSparseStep *stage;   // input order: two step slots per record
-    void *temp;
-    size_t temp_bytes;
+struct PphScratch {
+    ChainScratch chain;  // per push; cnt, offs and stage in input order
     PphScalars *sc;
 };
 
-size_t pph_temp_bytes(uint64_t n);
 // keys, sort by pixel, walk every pixel's run, scan the step counts; sc->bad and sc->steps are valid afterwards
 hipError_t pph_generate(const PphArgs &a, const uint8_t *d_records, uint64_t n, const PphScratch &s, hipStream_t stream);
 // places the steps in record order into d_steps and commits the walked pixels' state

@@ -73,7 +73,7 @@ static int ensure_scratch(AdderStream *v, uint64_t n, bool info) {
     if (n <= v->cap && (!info || n <= v->info_cap)) return ADDER_OK;
     const bool had_info = v->info_cap > 0;
     free_scratch(v);
-    const uint64_t c = n + n / 8u > (uint64_t)INT32_MAX ? (uint64_t)INT32_MAX : n + n / 8u;
+    const uint64_t c = scratch_capacity(n);
     SHIPCHK(v, hipMalloc((void **)&v->s.keys0, c * 4u));
     SHIPCHK(v, hipMalloc((void **)&v->s.keys1, c * 4u));
     SHIPCHK(v, hipMalloc((void **)&v->s.idx0, c * 4u));
@@ -164,8 +164,7 @@ extern "C" int adder_stream_create(const AdderStreamParams *p, AdderStream **out
     a.height = p->height;
     a.channels = p->channels;
     a.units = (uint32_t)units64;
-    a.key_bits = 1;
-    while ((1ull << a.key_bits) < (uint64_t)a.units + 1u) ++a.key_bits;  // keys 0..units (units: never worked on)
+    a.key_bits = key_bits_for(a.units);  // keys 0..units (units: never worked on)
     a.ref = p->ref_interval;
     // a v0 / v1 stream has no time-mode field: it is DeltaT
     const uint32_t in_mode = p->codec_version >= 2 ? p->time_mode : (uint32_t)ADDER_TIME_DELTA_T;

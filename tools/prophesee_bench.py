@@ -5,7 +5,7 @@ line per case (and, with OUT=<path>, writes them to that file too): records, eve
 call returns after the device is done) and camera records per second.  Cases: `hd` (the floored one), `skewed` (a
 few pixels hold long runs; reported only) and `mirror` (the C++ mirror, host_py.prophesee, on the first 2^20 records).
 The split between step generation and integration comes from a separate `rocprofv3 --kernel-trace --stats` run of
-the `hd` case (pph_* kernels vs adder_sparse_* kernels and the hipCUB sort / scan each side launches).
+the `hd` case (pph_* and chain_* kernels vs adder_sparse_* kernels and the hipCUB sort / scan each side launches).
 
     python tools/prophesee_bench.py       # env: CALLS, RATE, CASES=hd,skewed,mirror, OUT
 """
