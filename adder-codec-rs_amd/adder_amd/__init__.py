@@ -32,11 +32,13 @@ from . import color as _color
 from .color import to_gray_device, to_gray_host  # noqa: F401
 from . import davis as _davis
 from .davis import HipDavis, davis_to_adder, davis_to_adder_file, DAVIS_EVENT_DTYPE  # noqa: F401
+from . import fast_eval as _fast_eval
+from .fast_eval import HipFastEval  # noqa: F401
 
 
 def load():
     """Loads libadder_hip.so and binds every symbol include/adder_hip.h, adder_framer.h, adder_compressed.h,
-    adder_dvs.h, adder_quality.h, adder_prophesee.h, adder_stream.h, adder_player.h, adder_viz_player.h, adder_color.h and adder_davis.h declare;
+    adder_dvs.h, adder_quality.h, adder_prophesee.h, adder_stream.h, adder_player.h, adder_viz_player.h, adder_color.h, adder_davis.h and adder_fast.h declare;
     raises if one is missing."""
     L = _native.load()
     _dvs.load()
@@ -47,4 +49,5 @@ def load():
     _viz_player.load()
     _color.load()
     _davis.load()
+    _fast_eval.load()
     return L

@@ -144,6 +144,7 @@ SYMBOLS = {
     "adder_hip_set_feature_parameters": (_i32, [_vp, _u8, _u16]),
     "adder_hip_update_roi": (_i32, [_vp, _i32, _u16, _u16, _u16, _u16]),
     "adder_hip_feature_set": (_i32, [_vp, _vp]),
+    "adder_hip_feature_set_device": (_i32, [_vp, _vp, _vp]),
     "adder_hip_c_thresh_plane": (_i32, [_vp, _vp]),
     "adder_hip_last_new_features": (_u32, [_vp]),
     "adder_hip_frames_configure": (_i32, [_vp, _u32, _sz]),

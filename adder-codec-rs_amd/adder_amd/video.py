@@ -135,6 +135,19 @@ class HipVideo:
         N.check(self.h, self.L.adder_hip_feature_set(self.h, out.ctypes.data))
         return out
 
+    def feature_set_device(self, d_out=None, stream=None):
+        """The same plane into the uint8 CUDA tensor d_out ([rows][width]; None: a new one), queued on `stream` behind
+        every batch of this context, without a host synchronisation (adder_hip_feature_set_device)."""
+        import torch
+        if d_out is None:
+            dev = int(self.params.device_id)  # (-1: the current device, as adder_hip_create takes it)
+            d_out = torch.empty((self.rows, self.width), dtype=torch.uint8,
+                                device=f"cuda:{dev if dev >= 0 else torch.cuda.current_device()}")
+        assert d_out.is_cuda and d_out.is_contiguous() and d_out.numel() * d_out.element_size() >= self.rows * self.width
+        stream = getattr(stream, "cuda_stream", stream)
+        N.check(self.h, self.L.adder_hip_feature_set_device(self.h, d_out.data_ptr(), C.c_void_p(stream) if stream else None))
+        return d_out
+
     def c_thresh_plane(self):
         out = np.zeros(self.n_units, np.uint8)
         N.check(self.h, self.L.adder_hip_c_thresh_plane(self.h, out.ctypes.data))

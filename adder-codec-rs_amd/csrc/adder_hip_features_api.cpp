@@ -75,6 +75,32 @@ extern "C" int adder_hip_feature_set(AdderHipCtx *c, uint8_t *dst) {
     return ADDER_OK;
 }
 
+extern "C" int adder_hip_feature_set_device(AdderHipCtx *c, uint8_t *d_dst, void *stream) {
+    if (!c || !d_dst) return ADDER_E_BAD_PARAMS;
+    if (c->pending) return fail(c, ADDER_E_BAD_PARAMS, "a device batch is pending");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)c->rows * c->p.width;
+    if (!c->fset) {
+        HIPCHK(c, hipMemsetAsync(d_dst, 0, n, s));
+        return ADDER_OK;
+    }
+    if (!c->ri_copy_e) HIPCHK(c, hipEventCreateWithFlags(&c->ri_copy_e, hipEventDisableTiming));
+    if (!c->ri_src_e) HIPCHK(c, hipEventCreateWithFlags(&c->ri_src_e, hipEventDisableTiming));
+    // behind the host-pointer batches and adder_hip_reset's memsets, which queue on the context's stream (no device
+    // batch is pending); the next batch waits for the copy as it does for one of the running-intensities plane
+    HIPCHK(c, hipEventRecord(c->ri_src_e, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(s, c->ri_src_e, 0));
+    if (c->pending_stream && c->pending_stream != c->stream && c->pending_stream != s) {
+        HIPCHK(c, hipEventRecord(c->ri_src_e, c->pending_stream));
+        HIPCHK(c, hipStreamWaitEvent(s, c->ri_src_e, 0));
+    }
+    HIPCHK(c, hipMemcpyAsync(d_dst, c->fset, n, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipEventRecord(c->ri_copy_e, s));
+    c->ri_copy_pending = true;
+    return ADDER_OK;
+}
+
 extern "C" int adder_hip_c_thresh_plane(AdderHipCtx *c, uint8_t *dst) {
     if (!c || !dst) return ADDER_E_BAD_PARAMS;
     if (c->pending) return fail(c, ADDER_E_BAD_PARAMS, "a device batch is pending");

@@ -146,6 +146,9 @@ int adder_hip_feature_detect(AdderHipCtx *ctx, uint32_t *d_new_xy, uint32_t cap,
 int adder_hip_feature_apply(AdderHipCtx *ctx, const uint32_t *d_xy, uint32_t n, void *stream);
 /* VideoState::features as a membership plane: dst = [rows][width] bytes, 1 = the pixel is a feature. */
 int adder_hip_feature_set(AdderHipCtx *ctx, uint8_t *dst);
+/* The same plane into device memory, queued on `stream` (NULL: the default stream) behind every batch of this context,
+ * without a host synchronisation; a later batch waits for the copy.  All zeros before feature detection has run. */
+int adder_hip_feature_set_device(AdderHipCtx *ctx, uint8_t *d_dst, void *stream);
 /* every pixel's c_thresh as the NEXT frame will test it: dst = [rows][width][channels] bytes */
 int adder_hip_c_thresh_plane(AdderHipCtx *ctx, uint8_t *dst);
 /* features the last finished batch found new (diagnostics) */
