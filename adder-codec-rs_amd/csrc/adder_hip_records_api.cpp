@@ -90,7 +90,11 @@ static int expand_records_impl(AdderHipCtx *c, const AdderBandRecords *bands, ui
     if (c->poisoned) return refuse_poisoned(c);
     const uint32_t nf = bands[0].num_frames;
     const bool abs_t = c->p.time_mode == ADDER_TIME_ABSOLUTE_T;
-    if (nf == 0 || nf > kMaxChunk || nf > c->own.ftab_cap) return fail(c, ADDER_E_BAD_PARAMS, "bad num_frames (root integrates the same frames first)");
+    // root's share of an expansion is the time step's constants and the frames' running_t: those of its last batch.  A
+    // root that has integrated nothing since adder_hip_create / adder_hip_reset has neither (own.ftab_cap does not tell:
+    // the table is allocated with the context, and nothing has written it)
+    if (nf == 0 || nf > kMaxChunk || nf > c->own.ftab_cap || c->frames_done == 0)
+        return fail(c, ADDER_E_BAD_PARAMS, "bad num_frames (root integrates the same frames first)");
     const bool runs = (bands[0].record_bytes & (uint32_t)ADDER_RECORDS_RUNS) != 0u;  // lean-runs records (expansion format 6)
     for (uint32_t r = 0; r < n_bands; ++r)
         if (bands[r].num_frames != nf || bands[r].record_bytes != (lean_rec_bytes(abs_t) | (runs ? (uint32_t)ADDER_RECORDS_RUNS : 0u)) || !bands[r].d_counts ||

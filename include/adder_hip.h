@@ -431,6 +431,7 @@ int adder_hip_integrate_records_device(AdderHipCtx *ctx, const uint8_t *d_frames
 /* On root, after its own adder_hip_integrate_records_device of the SAME frames (root's frame table gives the frames'
  * running_t): bands[0 .. n_bands) in raster order, every pointer in root's memory.  Appends the frames' events to
  * d_merged at event index merged_base and writes d_merged_offsets[0 .. num_frames] (absolute: [0] = merged_base).
+ * A root that has integrated nothing since adder_hip_create / adder_hip_reset is ADDER_E_BAD_PARAMS.
  * Queues on `stream`; a d_merged too small is reported by the context's status at the next adder_hip_finish /
  * adder_hip_expand_status (events past merged_cap are dropped). */
 int adder_hip_expand_records_device(AdderHipCtx *root, const AdderBandRecords *bands, uint32_t n_bands, AdderEvent *d_merged,
