@@ -11,6 +11,8 @@
 //   4. an exclusive scan of the marks in input order places the DVS events, a thread per event stores them;
 //   5. commit: the walked units' state is copied back unless the output did not fit.
 // Everything past the first bad event (or EOF record) is left out of steps 3-5.
+// A context that enabled the event video takes the VIDEO arm of steps 3 and 5 and the kernels of adder_dvs_video.hip
+// between them; any other context launches exactly the steps above.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -80,10 +82,15 @@ __global__ __launch_bounds__(256) void dvs_ln_kernel(const void *__restrict__ in
     s_td[j] = (uint64_t)e.t | ((uint64_t)e.d << 32);
 }
 
+// VIDEO: the arm of a context with the event video enabled -- every walked event also leaves the unit's time after
+// it at its input index (0 for a unit's first event) and is counted for the count map.
+template <bool VIDEO>
 __global__ __launch_bounds__(256) void dvs_walk_kernel(uint64_t n, DvsArgs a, const uint32_t *__restrict__ keys,
                                                        const uint32_t *__restrict__ idx, const double *__restrict__ s_ln,
                                                        const uint64_t *__restrict__ s_td, uint8_t *__restrict__ flag,
-                                                       uint64_t *__restrict__ tout, const DvsScalars *sc) {
+                                                       uint64_t *__restrict__ tout, const DvsScalars *sc,
+                                                       uint64_t *__restrict__ v_pt, const uint32_t *__restrict__ v_cur_cnt,
+                                                       uint32_t *__restrict__ v_nxt_cnt) {
     const uint64_t j0 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (j0 >= n) return;
     const uint32_t u = keys[j0];
@@ -92,9 +99,11 @@ __global__ __launch_bounds__(256) void dvs_walk_kernel(uint64_t n, DvsArgs a, co
     bool init = a.cur_init[u] != 0u;
     double ln = a.cur_ln[u];
     uint64_t pt = a.cur_t[u];
+    uint32_t walked = 0u;
     for (uint64_t j = j0; j < n && keys[j] == u; ++j) {
         const uint32_t i = idx[j];
         if (i >= lim) break;
+        if (VIDEO) ++walked;
         const uint64_t td = s_td[j];
         const uint32_t d = (uint32_t)(td >> 32), t = (uint32_t)td;
         if (!init) {  // d <= 128 here: a first event with d > 128 set lim at or before it
@@ -106,6 +115,7 @@ __global__ __launch_bounds__(256) void dvs_walk_kernel(uint64_t n, DvsArgs a, co
         const uint64_t old_t = pt;
         pt = a.delta_t ? pt + t : (uint64_t)t;
         if (a.framed) pt = wire_round_up(pt, a.ref);
+        if (VIDEO) v_pt[i] = pt;
         if (d == 255u) continue;  // D_EMPTY: the time moved, nothing fires
         const double nw = s_ln[j];
         const bool win = nw > 0.406 && nw < 0.407;
@@ -127,6 +137,7 @@ __global__ __launch_bounds__(256) void dvs_walk_kernel(uint64_t n, DvsArgs a, co
     a.nxt_init[u] = init ? 1u : 0u;
     a.nxt_ln[u] = ln;
     a.nxt_t[u] = pt;
+    if (VIDEO) v_nxt_cnt[u] = v_cur_cnt[u] + walked;
 }
 
 struct DvsFired {
@@ -163,15 +174,21 @@ __global__ __launch_bounds__(256) void dvs_scatter_kernel(const void *__restrict
     }
 }
 
+// VIDEO: the video arm's verdict (the output and the frame ring both fit) decides, and the counts are committed too
+template <bool VIDEO>
 __global__ __launch_bounds__(256) void dvs_commit_kernel(uint64_t n, DvsArgs a, const uint32_t *__restrict__ keys,
-                                                         uint64_t out_cap, const DvsScalars *sc) {
+                                                         uint64_t out_cap, const DvsScalars *sc,
+                                                         const DvsVideoScalars *vs, uint32_t *__restrict__ v_cur_cnt,
+                                                         const uint32_t *__restrict__ v_nxt_cnt) {
     const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (j >= n || sc->total > out_cap) return;
+    if (j >= n) return;
+    if (VIDEO ? vs->ok == 0ull : sc->total > out_cap) return;
     const uint32_t u = keys[j];
     if (u >= a.units || (j > 0u && keys[j - 1] == u)) return;
     a.cur_init[u] = a.nxt_init[u];
     a.cur_ln[u] = a.nxt_ln[u];
     a.cur_t[u] = a.nxt_t[u];
+    if (VIDEO) v_cur_cnt[u] = v_nxt_cnt[u];
 }
 
 __global__ __launch_bounds__(256) void dvs_sort_keys_kernel(const void *__restrict__ rec, uint64_t n, int out_format,
@@ -210,7 +227,7 @@ size_t dvs_temp_bytes(uint64_t n) {
 
 template <int SRC>
 static hipError_t dvs_convert_src(const DvsArgs &a, const void *in, uint64_t n, int out_format, void *out,
-                                  uint64_t out_cap, const DvsScratch &s, hipStream_t stream) {
+                                  uint64_t out_cap, const DvsScratch &s, hipStream_t stream, const DvsVideoArgs *va) {
     const uint32_t grid = (uint32_t)((n + 255u) / 256u);
     size_t temp_bytes = s.temp_bytes;
     hipLaunchKernelGGL(dvs_init_kernel, dim3(1), dim3(1), 0, stream, s.sc, n);
@@ -222,23 +239,38 @@ static hipError_t dvs_convert_src(const DvsArgs &a, const void *in, uint64_t n, 
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((dvs_ln_kernel<SRC>), dim3(grid), dim3(256), 0, stream, in, n, a, k.Current(), v.Current(),
                        s.s_ln, s.s_td, s.sc);
-    hipLaunchKernelGGL(dvs_walk_kernel, dim3(grid), dim3(256), 0, stream, n, a, k.Current(), v.Current(), s.s_ln,
-                       s.s_td, s.flag, s.tout, s.sc);
+    if (va) {
+        e = hipMemsetAsync(va->pt, 0, n * 8u, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(dvs_walk_kernel<true>, dim3(grid), dim3(256), 0, stream, n, a, k.Current(), v.Current(),
+                           s.s_ln, s.s_td, s.flag, s.tout, s.sc, va->pt, va->cur_cnt, va->nxt_cnt);
+    } else {
+        hipLaunchKernelGGL(dvs_walk_kernel<false>, dim3(grid), dim3(256), 0, stream, n, a, k.Current(), v.Current(),
+                           s.s_ln, s.s_td, s.flag, s.tout, s.sc, nullptr, nullptr, nullptr);
+    }
     hipcub::TransformInputIterator<uint32_t, DvsFired, const uint8_t *> fired(s.flag, DvsFired());
     e = hipcub::DeviceScan::ExclusiveSum(s.temp, temp_bytes, fired, s.offs, (int)n, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((dvs_scatter_kernel<SRC>), dim3(grid), dim3(256), 0, stream, in, n, s.flag, s.tout, s.offs,
                        out_format, out, out_cap, s.sc);
-    hipLaunchKernelGGL(dvs_commit_kernel, dim3(grid), dim3(256), 0, stream, n, a, k.Current(), out_cap, s.sc);
+    if (va) {
+        e = dvs_video_schedule(a, *va, n, out_cap, s, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(dvs_commit_kernel<true>, dim3(grid), dim3(256), 0, stream, n, a, k.Current(), out_cap, s.sc,
+                           va->vs, va->cur_cnt, va->nxt_cnt);
+        return va->draw ? dvs_video_draw(a, *va, SRC, in, n, s, stream) : hipGetLastError();
+    }
+    hipLaunchKernelGGL(dvs_commit_kernel<false>, dim3(grid), dim3(256), 0, stream, n, a, k.Current(), out_cap, s.sc,
+                       nullptr, nullptr, nullptr);
     return hipGetLastError();
 }
 
 hipError_t dvs_convert(const DvsArgs &a, int source, const void *in, uint64_t n, int out_format, void *out,
-                       uint64_t out_cap, const DvsScratch &s, hipStream_t stream) {
+                       uint64_t out_cap, const DvsScratch &s, hipStream_t stream, const DvsVideoArgs *va) {
     if (n == 0u) return hipSuccess;
-    if (source == kSrcEvents) return dvs_convert_src<kSrcEvents>(a, in, n, out_format, out, out_cap, s, stream);
-    if (source == kSrcWire9) return dvs_convert_src<kSrcWire9>(a, in, n, out_format, out, out_cap, s, stream);
-    return dvs_convert_src<kSrcWire11>(a, in, n, out_format, out, out_cap, s, stream);
+    if (source == kSrcEvents) return dvs_convert_src<kSrcEvents>(a, in, n, out_format, out, out_cap, s, stream, va);
+    if (source == kSrcWire9) return dvs_convert_src<kSrcWire9>(a, in, n, out_format, out, out_cap, s, stream, va);
+    return dvs_convert_src<kSrcWire11>(a, in, n, out_format, out, out_cap, s, stream, va);
 }
 
 size_t dvs_sort_temp_bytes(uint64_t n) {

@@ -7,6 +7,10 @@
  *       examples/adder_to_dvs.c -Ladder-codec-rs_amd -ladder_hip -L$ROCM_PATH/lib -lamdhip64 \
  *       -Wl,-rpath,$PWD/adder-codec-rs_amd -o adder_to_dvs
  *   ./adder_to_dvs in.adder out.dat [--text] [--theta 0.01] [--reorder] [--date "2024-01-01 00:00:00"]
+ *       [--video out.gray8 [--fps 100] [--buffer-secs 10] [--no-draw]] [--counts out.counts]
+ *
+ * --video: the DVS event video as raw [n][h][w] gray8 planes (255 on, 0 off, 128 blank) and PATH.times, one line per
+ * written frame with the time the reference stamps it with; --counts: the event-count map, [h][w][3] bytes.
  */
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -20,14 +24,31 @@
 #define BATCH_RECORDS (1u << 22)
 
 static int usage(void) {
-    fprintf(stderr, "usage: adder_to_dvs IN.adder OUT [--text] [--theta T] [--reorder] [--date \"Y-m-d H:M:S\"]\n");
+    fprintf(stderr, "usage: adder_to_dvs IN.adder OUT [--text] [--theta T] [--reorder] [--date \"Y-m-d H:M:S\"]\n"
+                    "           [--video PATH] [--fps F] [--buffer-secs S] [--no-draw] [--counts PATH]\n");
     return 2;
 }
 
+/* Writes the frames that are ready to `vf` (when there is one) and counts them. */
+static int drain_video(AdderDvs *dvs, FILE *vf, size_t plane, uint64_t *frames) {
+    uint64_t k = 0, got = 0;
+    if (adder_dvs_video_frames_ready(dvs, &k) != ADDER_OK) return 1;
+    if (k == 0) return 0;
+    uint8_t *buf = malloc((size_t)k * plane);
+    if (!buf) return 1;
+    const int rc = adder_dvs_video_pop(dvs, buf, k, NULL, &got);
+    if (rc == ADDER_OK && vf) fwrite(buf, plane, got, vf);
+    free(buf);
+    if (rc != ADDER_OK) return 1;
+    *frames += got;
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    const char *in_path = NULL, *out_path = NULL, *date = NULL;
-    int text = 0, reorder = 0;
+    const char *in_path = NULL, *out_path = NULL, *date = NULL, *video_path = NULL, *counts_path = NULL;
+    int text = 0, reorder = 0, draw = 1;
     double theta = 0.01;
+    float fps = 100.0f, buffer_secs = 10.0f;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--text"))
             text = 1;
@@ -37,6 +58,16 @@ int main(int argc, char **argv) {
             theta = atof(argv[++i]);
         else if (!strcmp(argv[i], "--date") && i + 1 < argc)
             date = argv[++i];
+        else if (!strcmp(argv[i], "--video") && i + 1 < argc)
+            video_path = argv[++i];
+        else if (!strcmp(argv[i], "--counts") && i + 1 < argc)
+            counts_path = argv[++i];
+        else if (!strcmp(argv[i], "--fps") && i + 1 < argc)
+            fps = (float)atof(argv[++i]);
+        else if (!strcmp(argv[i], "--buffer-secs") && i + 1 < argc)
+            buffer_secs = (float)atof(argv[++i]);
+        else if (!strcmp(argv[i], "--no-draw"))
+            draw = 0;
         else if (!in_path)
             in_path = argv[i];
         else if (!out_path)
@@ -73,6 +104,23 @@ int main(int argc, char **argv) {
         fprintf(stderr, "adder_dvs_create -> %d: %s\n", rc, adder_dvs_last_error(NULL));
         return 1;
     }
+    const int video = video_path || counts_path;
+    const size_t plane = (size_t)p.width * p.height;
+    FILE *vf = NULL;
+    uint64_t frames = 0;
+    if (video) {
+        AdderDvsVideoParams vp;
+        if (adder_dvs_video_params_from_header(hdr, hl, &vp) != ADDER_OK) return 1; /* parsed above: cannot fail */
+        vp.fps = fps;
+        vp.buffer_secs = buffer_secs;
+        vp.draw = (uint32_t)draw;
+        rc = adder_dvs_video_enable(dvs, &vp);
+        if (rc != ADDER_OK) {
+            fprintf(stderr, "adder_dvs_video_enable -> %d: %s\n", rc, adder_dvs_last_error(dvs));
+            return 1;
+        }
+        if (video_path && !(vf = fopen(video_path, "wb"))) return perror(video_path), 1;
+    }
     FILE *g = fopen(out_path, "wb");
     if (!g) return perror(out_path), 1;
     const size_t hn = adder_dvs_header_bytes(p.width, p.height, date, !text, NULL, 0);
@@ -95,52 +143,70 @@ int main(int argc, char **argv) {
     size_t text_cap = 0;
     uint64_t n_in = 0, n_out = 0;
     int status = 0;
-    for (;;) {
-        const size_t n = fread(h_in, eb, BATCH_RECORDS, f);
-        if (n == 0) break;
-        if (hipMemcpy(d_in, h_in, n * eb, hipMemcpyHostToDevice) != hipSuccess) return 1;
-        uint64_t got = 0, bad = ADDER_DVS_NO_BAD_EVENT, consumed = 0;
-        rc = adder_dvs_convert_wire_device(dvs, d_in, n, fmt, d_out, BATCH_RECORDS, &got, &bad, &consumed, NULL);
-        if (rc != ADDER_OK && rc != ADDER_DVS_E_BAD_EVENT) {
-            fprintf(stderr, "convert -> %d: %s\n", rc, adder_dvs_last_error(dvs));
-            return 1;
-        }
-        if (reorder) {
-            if (kept_n + got > kept_cap) {
-                uint8_t *bigger = NULL;
-                while (kept_n + got > kept_cap) kept_cap *= 2;
-                if (hipMalloc((void **)&bigger, kept_cap * rb) != hipSuccess) return 1;
-                if (kept_n) hipMemcpy(bigger, d_kept, kept_n * rb, hipMemcpyDeviceToDevice);
-                hipFree(d_kept);
-                d_kept = bigger;
+    int done = 0;
+    while (!done) {
+        const size_t n_read = fread(h_in, eb, BATCH_RECORDS, f);
+        if (n_read == 0) break;
+        if (hipMemcpy(d_in, h_in, n_read * eb, hipMemcpyHostToDevice) != hipSuccess) return 1;
+        if (n_read < BATCH_RECORDS) done = 1; /* the end of the file */
+        /* one call per batch; with the video on, a batch that asks for more ring frames than there are changes
+         * nothing and is converted in smaller pieces */
+        for (size_t pos = 0, size = n_read; pos < n_read;) {
+            const size_t n = size < n_read - pos ? size : n_read - pos;
+            uint64_t got = 0, bad = ADDER_DVS_NO_BAD_EVENT, consumed = 0;
+            rc = adder_dvs_convert_wire_device(dvs, d_in + pos * eb, n, fmt, d_out, BATCH_RECORDS, &got, &bad,
+                                               &consumed, NULL);
+            if (rc == ADDER_E_OUT_CAPACITY && video && n >= 2) {
+                size = n / 2;
+                continue;
             }
-            if (got) hipMemcpy(d_kept + kept_n * rb, d_out, got * rb, hipMemcpyDeviceToDevice);
-            kept_n += got;
-        } else if (got) {
-            hipMemcpy(h_out, d_out, got * rb, hipMemcpyDeviceToHost);
-            if (text) {
-                const size_t tn = adder_dvs_format_text((const AdderDvsEvent *)h_out, got, NULL, 0);
-                if (tn > text_cap) {
-                    free(text_buf);
-                    text_cap = tn;
-                    text_buf = malloc(text_cap);
+            if (rc != ADDER_OK && rc != ADDER_DVS_E_BAD_EVENT) {
+                fprintf(stderr, "convert -> %d: %s\n", rc, adder_dvs_last_error(dvs));
+                return 1;
+            }
+            if (video && drain_video(dvs, vf, plane, &frames)) return 1;
+            if (reorder) {
+                if (kept_n + got > kept_cap) {
+                    uint8_t *bigger = NULL;
+                    while (kept_n + got > kept_cap) kept_cap *= 2;
+                    if (hipMalloc((void **)&bigger, kept_cap * rb) != hipSuccess) return 1;
+                    if (kept_n) hipMemcpy(bigger, d_kept, kept_n * rb, hipMemcpyDeviceToDevice);
+                    hipFree(d_kept);
+                    d_kept = bigger;
                 }
-                adder_dvs_format_text((const AdderDvsEvent *)h_out, got, text_buf, text_cap);
-                fwrite(text_buf, 1, tn, g);
-            } else {
-                fwrite(h_out, rb, got, g);
+                if (got) hipMemcpy(d_kept + kept_n * rb, d_out, got * rb, hipMemcpyDeviceToDevice);
+                kept_n += got;
+            } else if (got) {
+                hipMemcpy(h_out, d_out, got * rb, hipMemcpyDeviceToHost);
+                if (text) {
+                    const size_t tn = adder_dvs_format_text((const AdderDvsEvent *)h_out, got, NULL, 0);
+                    if (tn > text_cap) {
+                        free(text_buf);
+                        text_cap = tn;
+                        text_buf = malloc(text_cap);
+                    }
+                    adder_dvs_format_text((const AdderDvsEvent *)h_out, got, text_buf, text_cap);
+                    fwrite(text_buf, 1, tn, g);
+                } else {
+                    fwrite(h_out, rb, got, g);
+                }
             }
+            n_out += got;
+            if (rc == ADDER_DVS_E_BAD_EVENT) {
+                fprintf(stderr, "event %llu cannot be converted: %s\n", (unsigned long long)(n_in + bad),
+                        adder_dvs_last_error(dvs));
+                n_in += bad;
+                status = 1;
+                done = 1;
+                break;
+            }
+            n_in += consumed;
+            if (consumed < n) { /* EOF record */
+                done = 1;
+                break;
+            }
+            pos += n;
         }
-        n_out += got;
-        if (rc == ADDER_DVS_E_BAD_EVENT) {
-            fprintf(stderr, "event %llu cannot be converted: %s\n", (unsigned long long)(n_in + bad),
-                    adder_dvs_last_error(dvs));
-            n_in += bad;
-            status = 1;
-            break;
-        }
-        n_in += consumed;
-        if (consumed < n || n < BATCH_RECORDS) break; /* EOF record, or the end of the file */
     }
     if (reorder && status == 0 && kept_n) { /* an error leaves the queue unwritten, as in the reference */
         rc = adder_dvs_sort_device(dvs, d_kept, kept_n, fmt, NULL);
@@ -155,6 +221,32 @@ int main(int argc, char **argv) {
     }
     fclose(g);
     fclose(f);
+    if (video && status == 0) { /* the stream's end: the tail of the deque, then the count map */
+        rc = adder_dvs_video_finish(dvs);
+        if (rc != ADDER_OK || drain_video(dvs, vf, plane, &frames)) {
+            fprintf(stderr, "video finish -> %d: %s\n", rc, adder_dvs_last_error(dvs));
+            return 1;
+        }
+        if (counts_path) {
+            uint8_t *cm = malloc(plane * 3);
+            FILE *cf = fopen(counts_path, "wb");
+            if (!cm || !cf || adder_dvs_event_count_map(dvs, cm) != ADDER_OK) return perror(counts_path), 1;
+            fwrite(cm, 1, plane * 3, cf);
+            fclose(cf);
+            free(cm);
+        }
+    }
+    if (vf) {
+        fclose(vf);
+        char *tp = malloc(strlen(video_path) + 7);
+        sprintf(tp, "%s.times", video_path);
+        FILE *tf = fopen(tp, "wb");
+        if (!tf) return perror(tp), 1;
+        double t = 0.0; /* current_frame_time += 1.0 / fps as f64 after every written frame (main.rs:198-233) */
+        for (uint64_t k = 0; k < frames; ++k, t += 1.0 / (double)fps) fprintf(tf, "%.9f\n", t);
+        fclose(tf);
+        free(tp);
+    }
     printf("%llu ADDER events -> %llu DVS events\n", (unsigned long long)n_in, (unsigned long long)n_out);
     hipFree(d_in);
     hipFree(d_out);

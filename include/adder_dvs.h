@@ -92,6 +92,73 @@ int adder_dvs_convert_wire_host(AdderDvs *dvs, const uint8_t *wire, uint64_t n_r
  * AdderDvsEvent's t); equal times keep their order.  The caller keeps the whole output and sorts once at the end. */
 int adder_dvs_sort_device(AdderDvs *dvs, void *d_records, uint64_t n, int out_format, void *stream);
 
+/* ---- The DVS event video and the event-count map (main.rs:189-239, 288, 382-411, 424-448).  Off by default. ----
+ *
+ * The reference keeps a deque of gray frames [frame_count, end): before each ADDER event, when
+ * current_t > frame_count * L + B, it pops (writes) the front frame and frame_count advances -- also when the deque
+ * is empty, so those indices are skipped.  L = (tps as f32 / fps) as u128 ticks per frame, B = (tps as f32 *
+ * buffer_secs) as u128.  A fired DVS event {old_t + 1, x, y, p} belongs to frame (old_t + 1) / L: it sets pixel
+ * (y, x) to 255 (p = 1) or 0 (p = 0) on a 128 background, the deque growing to reach it, unless that frame was
+ * already popped (then the event is dropped from the video only).  The reference never joins its drawing call to its
+ * fire points; the join here is that of its sibling tool (bin_cv/aedat4_dvs_visualize.rs:132-145, 203-206), and
+ * draw = 0 gives the reference's literal output, blank frames.  Built here: the frames as [h][w] u8 planes (the
+ * reference's frame is that plane three times) with their frame indices, and the per-unit event-count map.  Not
+ * built: the mp4 encoder, the on-screen display, a viewer for plain .dat recordings.
+ *
+ * Pending frames live in a ring of ring_frames planes on the device, and so do the frames a call emitted until they
+ * are popped.  A convert call that needs more slots than the ring has returns ADDER_E_OUT_CAPACITY and changes
+ * nothing, like one whose DVS output does not fit; adder_dvs_video_ring_needed tells the slots it asked for. */
+typedef struct AdderDvsVideoParams {
+    uint32_t abi_version; /* = ADDER_DVS_ABI_VERSION */
+    uint32_t tps;         /* ticks per second (meta.tps) */
+    float fps;            /* finite, > 0, and tps / fps >= 1 (CLI default 100) */
+    float buffer_secs;    /* CLI default 10; negative and NaN count as 0 */
+    uint32_t ring_frames; /* 0: ceil(B / L) + 64 */
+    uint32_t draw;        /* 1: fired events are drawn; 0: the reference's literal blank frames */
+} AdderDvsVideoParams;
+
+/* Fills tps from the header of a raw .adder stream and the CLI's defaults: fps 100, buffer_secs 10, draw 1,
+ * ring_frames 0. */
+int adder_dvs_video_params_from_header(const uint8_t *buf, size_t len, AdderDvsVideoParams *p);
+/* Enables the video and the count map.  Only on a context that converted no event since its create or last reset
+ * (adder_dvs_reset also puts the video back to its start).  ADDER_E_BAD_PARAMS: fps not finite or not positive, L = 0. */
+int adder_dvs_video_enable(AdderDvs *dvs, const AdderDvsVideoParams *p);
+/* The frames emitted by the convert calls (and the finish) since the last pop. */
+int adder_dvs_video_frames_ready(AdderDvs *dvs, uint64_t *n);
+/* Ring slots the last convert or finish call needed (at most ring_frames unless it failed for them). */
+int adder_dvs_video_ring_needed(AdderDvs *dvs, uint64_t *n);
+/* Hands the ready frames out, oldest first, as [*n_popped][h][w] bytes to `d_out` (device) / `out` (host), and their
+ * frame indices to frame_index (a host array of out_cap_frames entries in both forms, may be null).  More ready frames
+ * than out_cap_frames: ADDER_E_OUT_CAPACITY with their number in *n_popped, nothing changes. */
+int adder_dvs_video_pop_device(AdderDvs *dvs, uint8_t *d_out, uint64_t out_cap_frames, uint64_t *frame_index,
+                               uint64_t *n_popped, void *stream);
+int adder_dvs_video_pop(AdderDvs *dvs, uint8_t *out, uint64_t out_cap_frames, uint64_t *frame_index,
+                        uint64_t *n_popped);
+/* The stream's end: the final check, then every pending frame (one blank frame when there is none) becomes ready.
+ * After a bad event this check is the one the reference makes in front of the event that fails: the stream ends there.
+ * Convert calls are refused afterwards, until a reset. */
+int adder_dvs_video_finish(AdderDvs *dvs);
+/* The event-count map, [h][w][3] bytes: 128 everywhere, and for c < channels
+ * ((count as u16) as f32 / m as f32 * 255.0) as u8 with m = min(largest count of a unit, 65535). */
+int adder_dvs_event_count_map_device(AdderDvs *dvs, uint8_t *d_out, void *stream);
+int adder_dvs_event_count_map(AdderDvs *dvs, uint8_t *out);
+/* ---- For self-tests only (as adder_dvs_log1p below): the video's arithmetic on the host, without a device.  A program
+ * that converts streams needs none of the five. ---- */
+/* What adder_dvs_video_enable asks of `p`, without a context: ADDER_OK or ADDER_E_BAD_PARAMS; *L and *B (may be null)
+ * receive the frame length and the buffer in ticks. */
+int adder_dvs_video_params_check(const AdderDvsVideoParams *p, uint64_t *L, uint64_t *B);
+/* L, B, and one byte of the count map. */
+uint64_t adder_dvs_video_frame_length(uint32_t tps, float fps);
+uint64_t adder_dvs_video_buffer_ticks(uint32_t tps, float buffer_secs);
+uint8_t adder_dvs_video_count_byte(uint32_t count, uint32_t m);
+/* The schedule of one call as the kernels compute it (adder_dvs_video_logic.hpp): pt[i] = the unit's time after
+ * event i (0: a first event), fire_t[i] = old_t + 1 of a fired event (0: none), state = {frame_count, current_t, end},
+ * in and out.  Returns the number of emitted frames; pop / accept (n marks each) and emitted (cap indices) may be
+ * null. */
+uint64_t adder_dvs_video_schedule_host(const uint64_t *pt, const uint64_t *fire_t, uint64_t n, uint64_t L, uint64_t B,
+                                       int draw, uint64_t *state, uint8_t *pop, uint8_t *accept, uint64_t *emitted,
+                                       uint64_t cap);
+
 /* Host helpers.  The .dat / text header: "% Height h\n% Width w\n% Version 2\n% Date <date>\n% end\n", and in binary
  * mode the two bytes 00 08.  Returns the header's length; writes it when it fits in cap bytes. */
 size_t adder_dvs_header_bytes(uint16_t width, uint16_t height, const char *date, int binary, char *out, size_t cap);
