@@ -34,6 +34,8 @@ from . import davis as _davis
 from .davis import HipDavis, davis_to_adder, davis_to_adder_file, DAVIS_EVENT_DTYPE  # noqa: F401
 from . import fast_eval as _fast_eval
 from .fast_eval import HipFastEval  # noqa: F401
+from . import compressed_model as _compressed_model
+from .compressed_model import HipCompressedModel, compress_events_device  # noqa: F401
 
 
 def load():
@@ -50,4 +52,5 @@ def load():
     _color.load()
     _davis.load()
     _fast_eval.load()
+    _compressed_model.load()
     return L

@@ -229,6 +229,7 @@ SYMBOLS = {
     "adder_compressed_encoder_destroy": (None, [_vp]),
     "adder_compressed_last_error": (C.c_char_p, [_vp]),
     "adder_compressed_encoder_ingest": (_i32, [_vp, _vp, _sz]),
+    "adder_compressed_encoder_ingest_symbols": (_i32, [_vp, _vp, _sz]),
     "adder_compressed_encoder_close": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
     "adder_compressed_encoder_progress": (_i32, [_vp, C.POINTER(_u32), C.POINTER(_sz)]),
     "adder_compressed_decode": (_i32, [_vp, _sz, _i32, C.POINTER(AdderCompressedParams), _vp, _sz, C.POINTER(_sz)]),

@@ -31,6 +31,14 @@ class CompressedEncoder:
         events = np.ascontiguousarray(events, dtype=N.EVENT_DTYPE)
         _check(self.h, self.L.adder_compressed_encoder_ingest(self.h, events.ctypes.data, len(events)))
 
+    def ingest_symbols(self, symbols):
+        """One whole ADU as the source model's symbol words (uint16: context << 10 | fenwick index, start_t first, eof
+        last; HipCompressedModel makes them), range coded on the worker pool and appended in ADU order.  An encoder
+        takes events or symbols, not both."""
+        s = np.ascontiguousarray(symbols)
+        s = s.view(np.uint16) if s.dtype.itemsize == 2 else s.astype(np.uint16)
+        _check(self.h, self.L.adder_compressed_encoder_ingest_symbols(self.h, s.ctypes.data, len(s)))
+
     def progress(self):
         a, n = C.c_uint32(0), C.c_size_t(0)
         _check(self.h, self.L.adder_compressed_encoder_progress(self.h, C.byref(a), C.byref(n)))

@@ -334,6 +334,8 @@ struct AduJob {  // one ADU on its way to a worker
     uint32_t id = 0;
     uint32_t start_t = 0;
     std::vector<std::vector<CubeEvent>> cubes;  // [by * bx], row-major
+    bool from_symbols = false;                  // the model ran elsewhere (adder_compressed_encoder_ingest_symbols):
+    std::vector<uint16_t> symbols;              // the ADU's (context, fenwick index) words, checked at ingest
 };
 
 // EventAdu::compress (event_adu.rs:83-117) -> the ADU's bytes
@@ -435,6 +437,20 @@ static std::vector<uint8_t> compress_adu(AduJob &job, uint32_t channels, uint32_
     return std::move(bw.bytes);
 }
 
+// The same coder over an ADU whose source model ran elsewhere (csrc/adder_compressed_logic.hpp's symbol words:
+// context << 10 | fenwick index, contexts d / t / bitshift / eof).  The words were checked when they were taken in.
+static std::vector<uint8_t> encode_symbols(const std::vector<uint16_t> &symbols) {
+    BitWriter bw;
+    Model m;
+    ArithEncoder enc;
+    enc.out = &bw;
+    Weights *const ctx[4] = {&m.d, &m.t, &m.bitshift, &m.eof};
+    for (const uint16_t w : symbols) enc.encode(*ctx[w >> 10], (size_t)(w & 1023u));
+    enc.flush();
+    bw.align();
+    return std::move(bw.bytes);
+}
+
 static size_t write_header(uint8_t *h, const AdderCompressedParams &p) {  // header.rs + encoder.rs:170-229
     size_t n = 0;
     memcpy(h, "addec", 5);
@@ -474,6 +490,7 @@ struct AdderCompressedEncoder {
     std::vector<std::pair<uint32_t, std::vector<uint8_t>>> done;  // finished, not yet appended (any order)
     bool stopping = false;
     bool closed = false;
+    int fed_by = 0;  // 0 nothing yet, 1 events (ingest), 2 symbols (ingest_symbols): one encoder takes one of the two
     std::string err;
 };
 
@@ -503,7 +520,9 @@ static void worker_loop(AdderCompressedEncoder *e) {
             e->jobs.pop_front();
         }
         std::vector<uint8_t> bytes =
-            compress_adu(*job, e->p.channels, e->p.ref_interval, e->p.adu_interval, e->p.c_thresh_max);
+            job->from_symbols
+                ? encode_symbols(job->symbols)
+                : compress_adu(*job, e->p.channels, e->p.ref_interval, e->p.adu_interval, e->p.c_thresh_max);
         {
             std::lock_guard<std::mutex> lk(e->mu);
             e->done.emplace_back(job->id, std::move(bytes));
@@ -612,6 +631,8 @@ extern "C" const char *adder_compressed_last_error(const AdderCompressedEncoder 
 extern "C" int adder_compressed_encoder_ingest(AdderCompressedEncoder *e, const AdderEvent *events, size_t n) {
     if (!e || (!events && n)) return ADDER_E_BAD_PARAMS;
     if (e->closed) return cfail(e, ADDER_E_BAD_PARAMS, "encoder is closed");
+    if (e->fed_by == 2) return cfail(e, ADDER_E_BAD_PARAMS, "this encoder takes symbols (ingest_symbols), not events");
+    if (n) e->fed_by = 1;
     const uint32_t span = e->p.ref_interval * e->p.adu_interval;
     for (size_t i = 0; i < n; ++i) {
         const AdderEvent &ev = events[i];
@@ -624,6 +645,47 @@ extern "C" int adder_compressed_encoder_ingest(AdderCompressedEncoder *e, const 
         e->cubes[cb].push_back(CubeEvent{(uint16_t)(c * 256u + (ev.y % kBlock) * kBlock + ev.x % kBlock), ev.d, ev.t});
         e->skip_adu = false;
     }
+    return ADDER_OK;
+}
+
+extern "C" int adder_compressed_encoder_ingest_symbols(AdderCompressedEncoder *e, const uint16_t *symbols, size_t n) {
+    if (!e || !symbols) return ADDER_E_BAD_PARAMS;
+    if (e->closed) return cfail(e, ADDER_E_BAD_PARAMS, "encoder is closed");
+    if (e->fed_by == 1) return cfail(e, ADDER_E_BAD_PARAMS, "this encoder takes events (ingest), not symbols");
+    // one whole ADU: four start_t bytes through the t context first, the eof symbol last and nowhere else
+    static const uint32_t entries[4] = {514, 257, 17, 2};  // the Model's fenwick tables (d, t, bitshift, eof)
+    if (n < 5) return cfail(e, ADDER_E_BAD_PARAMS, "%zu symbols are no ADU (start_t and eof alone are 5)", n);
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t ctx = symbols[i] >> 10, index = symbols[i] & 1023u;
+        if (ctx > 3 || index >= entries[ctx])
+            return cfail(e, ADDER_E_BAD_PARAMS, "symbol %zu (0x%04x): context %u has no index %u", i, symbols[i], ctx, index);
+        if ((ctx == 3) != (i + 1 == n) || (ctx == 3 && index != 0))
+            return cfail(e, ADDER_E_BAD_PARAMS, i + 1 == n ? "the ADU's last symbol (0x%04x at %zu) is not eof"
+                                                           : "eof symbol (0x%04x) at %zu, before the ADU's end",
+                         symbols[i], i);
+    }
+    uint32_t start_t = 0;
+    for (size_t i = 0; i < 4; ++i) {
+        if ((symbols[i] >> 10) != 1 || (symbols[i] & 1023u) == 0)
+            return cfail(e, ADDER_E_BAD_PARAMS, "symbol %zu is no start_t byte", i);
+        start_t = start_t << 8 | ((symbols[i] & 1023u) - 1u);
+    }
+    if (start_t != e->start_t)
+        return cfail(e, ADDER_E_BAD_PARAMS, "symbols of the ADU that starts at %u, the encoder's next ADU starts at %u",
+                     start_t, e->start_t);
+    e->fed_by = 2;
+    std::unique_ptr<AduJob> job(new AduJob());
+    job->id = e->next_id++;
+    job->start_t = e->start_t;
+    job->from_symbols = true;
+    job->symbols.assign(symbols, symbols + n);
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        e->jobs.push_back(std::move(job));
+        drain_in_order(e);
+    }
+    e->cv_job.notify_one();
+    e->start_t += e->p.adu_interval * e->p.ref_interval;  // as submit_adu
     return ADDER_OK;
 }
 

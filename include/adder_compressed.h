@@ -16,6 +16,11 @@
  * of the lossy bit shift (cabac_contexts.rs:75-150): byte-identical to the restatement in
  * oracle/compressed_oracle.py, which is pinned by the reference's own round-trip tests.
  *
+ * Only the adaptive range coder is serial.  The source model in front of it (ADU cut, cube / pixel grouping, intra
+ * and inter residuals, the lossy bit shift) also exists on the device: include/adder_compressed_model.h turns events
+ * in HBM into the coder's symbol words and the decoder-exact reconstructed events, and
+ * adder_compressed_encoder_ingest_symbols below codes those words.  This sink stays the default.
+ *
  * A Rust host binds these with `extern "C"` in place of CompressedOutput::ingest_event / into_writer. */
 #ifndef ADDER_COMPRESSED_H
 #define ADDER_COMPRESSED_H
@@ -54,6 +59,13 @@ void adder_compressed_encoder_destroy(AdderCompressedEncoder *e);
 const char *adder_compressed_last_error(const AdderCompressedEncoder *e);
 /* Encoder::ingest_events -> CompressedOutput::ingest_event (stream.rs:268-319), n events in stream order. */
 int adder_compressed_encoder_ingest(AdderCompressedEncoder *e, const AdderEvent *events, size_t n);
+/* One whole ADU as the (context, fenwick index) words of include/adder_compressed_model.h (context << 10 | index;
+ * contexts 0 d, 1 t, 2 bitshift, 3 eof): four start_t bytes through the t context first, eof last.  The ADU is range
+ * coded on the worker pool with a fresh model and appended in order, exactly as an ADU of _ingest is; the encoder's
+ * start_t advances by one ADU.  An encoder takes events or symbols, never both: the other call is refused, as is a
+ * word with an unknown context or an index outside its context's table, an ADU without its eof, and an ADU whose
+ * start_t is not the encoder's. */
+int adder_compressed_encoder_ingest_symbols(AdderCompressedEncoder *e, const uint16_t *symbols, size_t n);
 /* Encoder::close_writer -> CompressedOutput::into_writer (stream.rs:179-262): compresses the partial last ADU,
  * waits for every ADU and hands out the whole stream (header + ADUs); the pointer stays valid until destroy. */
 int adder_compressed_encoder_close(AdderCompressedEncoder *e, const uint8_t **bytes, size_t *n_bytes);
